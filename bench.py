@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the batched physics step (BASELINE.json metric).
 
-    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workloads = BASELINE.json configs; the default is config 2, the one the metric is quoted on:
 
@@ -28,11 +28,24 @@ ranks on 127.0.0.1 (one GPU each); under a launcher the world size must equal --
 fewer than N GPUs the run fails too, unless DMC_BENCH_SINGLE_DEVICE=1 (+ DMC_BENCH_BACKEND=gloo) asks for all ranks on
 cuda:0 -- a harness check, not a measurement.
 
-roofline.traffic and roofline_issue are measured IN THE RUN when rocprofv3 is on the PATH (N = 1): the bench re-runs
+With --full, roofline.traffic and roofline_issue are measured IN THE RUN when rocprofv3 is on the PATH (N = 1): the bench re-runs
 itself (`--pmc-child`: same workload, 30 steps, nothing else) under `rocprofv3 --kernel-trace --pmc <counters>` once per
 counter group -- FETCH_SIZE and WRITE_SIZE in separate passes, reads x 2 as MI355X_MICROARCH.md prescribes for gfx950
 -- and reads the timed launches' rows from the csv.  DMC_BENCH_NO_PMC=1 (or an enclosing rocprofv3) skips the passes;
 the line then carries the committed counters of profiles/ and says so in `traffic_source`.
+
+A plain run sets up, warms up, times the K launches and prints the headline (`value`, `ms_per_step` = wall-clock
+milliseconds of one timed launch); `roofline` then carries the committed counters of profiles/.  Everything else -- the
+rollout and pipelined legs, the collectives (N > 1), the live rocprofv3 counter passes, the parity check against the CPU
+oracle, the CPU baseline and the short legs of the other configs under `extra` -- runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed launches left behind after the last of them (qpos, qvel and the config's
+outputs: sensordata, xpos, xmat, subtree_com) as DIR/<name>.npy (float32 for an fp32 run, float64 for fp64; a fixed,
+seeded sample of the environments if the whole batch would exceed 64 MB; ranks > 0 add `.rank<r>` to the name).  Start
+states and actions are seeded, so two builds run with the same arguments can be compared array for array.
+
+The metric string names the max rel qpos error vs CPU; that figure (`max_rel_qpos_err_vs_cpu`, `parity`) is in the line
+only with --full.
 
 Prints ONE JSON line on rank 0.
 """
@@ -93,9 +106,14 @@ def parse(argv=None):
   ap.add_argument('--cpu-seconds', type=float, default=10.0)
   ap.add_argument('--pmc-child', action='store_true', help='internal: only the timed launches (run under rocprofv3 by the parent)')
   ap.add_argument('--extra', type=int, default=None,
-                  help='short legs of the other BASELINE configs (3, 4, 5) and of Environment.step on config 2 under "extra" '
-                       '(default: on for the default invocation -- config 2 on one GPU -- off otherwise)')
+                  help='with --full: short legs of the other BASELINE configs (3, 4, 5) and of Environment.step on config 2 under '
+                       '"extra" (default: on for the default invocation -- config 2 on one GPU -- off otherwise)')
   ap.add_argument('--extra-steps', type=int, default=12, help='timed launches of each extra config leg (>= 10)')
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline: rollout / pipelined / collective legs, live rocprofv3 counters, parity vs the CPU '
+                       'oracle, CPU baseline and the `extra` legs (a plain run times the K launches and nothing else)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the arrays the timed launches produced (state after the last one) to DIR/<name>.npy')
   return ap.parse_args(argv)
 
 
@@ -252,6 +270,16 @@ def threaded_rollout(phys, acts, nsub, nthreads):
   return len(shards)
 
 
+def host_threads():
+  """Host threads of the oracle legs: the CPUs this process may use, capped by OMP_NUM_THREADS where that is set."""
+  n = len(os.sched_getaffinity(0))
+  try:
+    n = min(n, int(os.environ.get('OMP_NUM_THREADS', '').split(',')[0]))
+  except ValueError:
+    pass
+  return max(1, n)
+
+
 def cpu_baseline(model, nsub, q0, v0, w0, action_fn, nthreads, target_s):
   """Times the fp64 oracle (oracle/, test infrastructure) on the host cores over a bounded sample of the same
   workload (~target_s seconds of wall clock).  kind = 'port': MuJoCo itself is not installable here."""
@@ -271,10 +299,10 @@ def cpu_baseline(model, nsub, q0, v0, w0, action_fn, nthreads, target_s):
   t0 = time.time()
   threaded_rollout(phys, acts, nsub, nthreads)
   dt = time.time() - t0
-  return dict(value=T * n / dt, unit='env-steps/s', cores=cores, kind='port',
+  return dict(value=T * n / dt, unit='env-steps/s', cores=cores, host_threads=nthreads, kind='port',
               physics_steps_per_s=T * n * nsub / dt,
-              sample='%d envs x %d env-steps x %d substeps (%.1f s wall), fp64 C restatement of mj_step (oracle/), one '
-                     'thread per core' % (n, T, nsub, dt))
+              sample='%d envs x %d env-steps x %d substeps (%.1f s wall), fp64 C restatement of mj_step (oracle/), %d host '
+                     'threads (the CPUs this process may use)' % (n, T, nsub, dt, nthreads))
 
 
 def mujoco_baseline(asset, nsub, q0, action_fn, nthreads, target_s):
@@ -315,7 +343,7 @@ def mujoco_baseline(asset, nsub, q0, action_fn, nthreads, target_s):
   t0 = time.time()
   run(acts)
   dt = time.time() - t0
-  return dict(value=T * n / dt, unit='env-steps/s', cores=len(shards), kind='mujoco',
+  return dict(value=T * n / dt, unit='env-steps/s', cores=len(shards), host_threads=nthreads, kind='mujoco',
               sample='%d envs x %d env-steps x %d substeps (%.1f s wall), mujoco %s mj_step, one MjData per thread'
                      % (n, T, nsub, dt, mujoco.__version__))
 
@@ -327,6 +355,26 @@ def _committed_pmc(config):
       return json.load(f)
   except Exception:  # pylint: disable=broad-except
     return None
+
+
+def dump_outputs(phys, cfg, directory, precision, rank=0, limit=64 << 20):
+  """--dump-outputs: the state the timed launches left (qpos, qvel and the config's outputs) as <directory>/<name>.npy.
+  Over `limit` bytes in all, a fixed seeded sample of the environments (the same rows in every array; `env_index.npy`
+  lists them)."""
+  names = ['qpos', 'qvel'] + [{'sensor': 'sensordata'}.get(o, o) for o in cfg['outputs']]
+  dtype = np.float32 if precision == 32 else np.float64
+  arrays = {n: phys.get(n).astype(dtype) for n in names}
+  B = phys.batch_size
+  per_env = sum(a[0].nbytes for a in arrays.values())
+  if per_env * B > limit:
+    keep = np.sort(np.random.RandomState(0).choice(B, max(1, (limit - 8 * B) // per_env), replace=False))
+    arrays = {n: a[keep] for n, a in arrays.items()}
+    arrays['env_index'] = keep.astype(np.float64)
+  os.makedirs(directory, exist_ok=True)
+  suffix = '' if rank == 0 else '.rank%d' % rank
+  for n, a in arrays.items():
+    np.save(os.path.join(directory, n + suffix + '.npy'), np.ascontiguousarray(a))
+  return sorted(arrays)
 
 
 def rel_err(qg, qo):
@@ -665,35 +713,45 @@ def main():
   if args.pmc_child:                         # the parent reads the last K step_kernel dispatches from rocprofv3's csv
     phys.close()
     return
+  if args.dump_outputs:
+    dump_outputs(phys, cfg, args.dump_outputs, args.precision, rank)
   q_end, v_end, w_end = phys.get('qpos'), phys.get('qvel'), phys.get('qacc_warmstart')
   warn = phys.get('warning').sum(axis=0)
   stats = dict(mean_ncon=float(phys.get('ncon').mean()), max_ncon=int(phys.get('ncon').max()),
                mean_nefc=float(phys.get('nefc').mean()), mean_solver_iter=float(phys.get('solver_iter').mean()))
 
-  # ---- rollout leg: the same K env-steps, same resident action tensor, ONE launch per
+  # ---- rollout leg (--full): the same K env-steps, same resident action tensor, ONE launch per
   # chunk of <= 250 steps, per-step qpos/qvel/sensordata written to HBM (dmc_batch_rollout)
-  chunk = min(250, K)
-  nchunks = max(1, K // chunk)
-  qs = torch.empty((chunk, model.nq, B), dtype=tdtype, device=dev)
-  vs = torch.empty((chunk, model.nv, B), dtype=tdtype, device=dev)
-  ss = torch.empty((chunk, max(1, model.nsensordata), B), dtype=tdtype, device=dev)
-  phys.rollout(min(W, chunk) or 1, nsub, actions[0:].data_ptr(), qs.data_ptr(), vs.data_ptr(), ss.data_ptr(), stream=stream)
-  torch.cuda.synchronize()
-  barrier()
-  torch.cuda.synchronize()
-  r0 = time.perf_counter()
-  for c in range(nchunks):
-    phys.rollout(chunk, nsub, actions[W + c*chunk:].data_ptr(), qs.data_ptr(), vs.data_ptr(), ss.data_ptr(), stream=stream)
-  torch.cuda.synchronize()
-  barrier()
-  torch.cuda.synchronize()
-  rollout_elapsed = max_over_ranks(time.perf_counter() - r0)
+  rollout = None
+  if args.full:
+    chunk = min(250, K)
+    nchunks = max(1, K // chunk)
+    qs = torch.empty((chunk, model.nq, B), dtype=tdtype, device=dev)
+    vs = torch.empty((chunk, model.nv, B), dtype=tdtype, device=dev)
+    ss = torch.empty((chunk, max(1, model.nsensordata), B), dtype=tdtype, device=dev)
+    phys.rollout(min(W, chunk) or 1, nsub, actions[0:].data_ptr(), qs.data_ptr(), vs.data_ptr(), ss.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    barrier()
+    torch.cuda.synchronize()
+    r0 = time.perf_counter()
+    for c in range(nchunks):
+      phys.rollout(chunk, nsub, actions[W + c*chunk:].data_ptr(), qs.data_ptr(), vs.data_ptr(), ss.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    barrier()
+    torch.cuda.synchronize()
+    rollout_elapsed = max_over_ranks(time.perf_counter() - r0)
+    rollout = {'value': world * B * nchunks * chunk / rollout_elapsed, 'unit': 'env-steps/s',
+               'steps': nchunks * chunk, 'launches': nchunks,
+               'note': 'same workload via dmc_batch_rollout: per-step actions read from / per-step '
+                       'qpos,qvel,sensordata written to HBM, no launch per step; `value` above is the '
+                       'host-in-the-loop mode (one Physics.step() launch per env-step)'}
 
   # ---- pipelined leg: the SAME B environments as P independent part-batches on P streams (part p's launch t+1 waits for
   # part p's launch t only, so the straggler tail of one part's queued launch overlaps the next part's launch).  A usage
-  # mode of the existing API (P BatchedPhysics objects), reported beside `value`, never as `value`.
+  # mode of the existing API (P BatchedPhysics objects), reported beside `value`, never as `value`.  (--full)
   pipe, pipes = None, []
-  for P in [int(x) for x in str(args.pipeline).split(',') if x.strip()]:
+  part_counts = [int(x) for x in str(args.pipeline).split(',') if x.strip()] if args.full else []
+  for P in part_counts:
     if not (P > 1 and B % P == 0):
       continue
     Bp = B // P
@@ -744,9 +802,9 @@ def main():
   if pipes:      # `pipelined`: the best part count; every count measured is listed under `by_parts`
     pipe = dict(max(pipes, key=lambda d_: d_['value']), by_parts={str(d_['parts']): d_['value'] for d_ in pipes})
 
-  # ---- agent-interface collectives (N > 1): actions scattered from rank 0, observations gathered to all ranks
+  # ---- agent-interface collectives (N > 1, --full): actions scattered from rank 0, observations gathered to all ranks
   coll = None
-  if world > 1:
+  if world > 1 and args.full:
     nobs = model.nq + model.nv + model.nsensordata
     glob_act = torch.rand((B * world, model.nu), device=red_dev) if rank == 0 else None
     obs = torch.cat([phys_t for phys_t in (torch.zeros((B, nobs), device=red_dev),)], dim=0)
@@ -828,7 +886,12 @@ def main():
     value = world * B * K / elapsed
     algo = cfg['algo_bytes']
     achieved = algo * B / (kernel_ms * 1e-3) / 1e9
-    live, why = (None, 'N > 1') if world > 1 else collect_pmc(args, 30)
+    if world > 1:
+      live, why = None, 'N > 1'
+    elif not args.full:
+      live, why = None, 'a plain run; --full measures them'
+    else:
+      live, why = collect_pmc(args, 30)
     pmc_source = 'live: rocprofv3 --pmc passes of this run (bench.py --pmc-child, 30 launches per pass)'
     if live and 'FETCH_SIZE' in live and 'WRITE_SIZE' in live:
       pmc = dict(live)
@@ -871,12 +934,9 @@ def main():
         'roofline': roof,
         'workload_stats': stats,
         'warnings_after_run': [int(x) for x in warn],
-        'rollout': {'value': world * B * nchunks * chunk / rollout_elapsed, 'unit': 'env-steps/s',
-                    'steps': nchunks * chunk, 'launches': nchunks,
-                    'note': 'same workload via dmc_batch_rollout: per-step actions read from / per-step '
-                            'qpos,qvel,sensordata written to HBM, no launch per step; `value` above is the '
-                            'host-in-the-loop mode (one Physics.step() launch per env-step)'},
     }
+    if rollout:
+      out['rollout'] = rollout
     if pmc and pmc.get('SQ_INSTS_VALU'):
       # what actually limits the kernel: VALU issue.  achieved = wave64 VALU instructions per launch (counter) x the issue
       # cost of one instruction / (1024 SIMDs x clock x kernel time of THIS run's HIP events: counter collection slows
@@ -898,12 +958,12 @@ def main():
       out['pipelined'] = pipe
     if coll:
       out['collectives'] = coll
-    nthreads = os.cpu_count() or 1
-    # ---- parity vs the CPU oracle on the first envs (checker only, untimed) -------
+    nthreads = host_threads()
+    # ---- parity vs the CPU oracle on the first envs (checker only, untimed; --full) -------
     try:
       ne = min(args.parity_envs if args.parity_envs is not None else cfg['parity_envs'], B)
       T = args.parity_steps if args.parity_steps is not None else cfg['parity_steps']
-      if T > 0 and ne > 0:
+      if args.full and T > 0 and ne > 0:
         pa = np.random.RandomState(77).uniform(-1, 1, (T, ne, model.nu)).astype(np.float32)
         res = parity(model, cfg, args, local_rank, q_start[:ne], v_start[:ne], w_start[:ne], pa, nthreads)
         out['max_rel_qpos_err_vs_cpu'] = res['open-loop']['max']
@@ -913,8 +973,8 @@ def main():
     except Exception as ex:  # pylint: disable=broad-except
       out['max_rel_qpos_err_vs_cpu'] = None
       out['parity_error'] = repr(ex)
-    # ---- CPU baseline (rank 0, N = 1 only; bounded sample) ----------------------------
-    if world == 1 and not args.no_cpu_baseline:
+    # ---- CPU baseline (rank 0, N = 1 only, --full; bounded sample) ----------------------------
+    if args.full and world == 1 and not args.no_cpu_baseline:
       nb = min(args.cpu_envs, B)
 
       def action_fn(t0, n):
@@ -927,7 +987,7 @@ def main():
       except Exception as ex:  # pylint: disable=broad-except
         out['cpu_baseline'] = {'value': None, 'error': repr(ex)}
     do_extra = args.extra if args.extra is not None else int(args.config == 2 and world == 1 and args.batch is None and args.precision == 32)
-    if do_extra:
+    if args.full and do_extra:
       # the other BASELINE configs and row a1 in the driver's line; each leg reports its own seconds
       extra = {'configs': {}}
       for c in (3, 4, 5):

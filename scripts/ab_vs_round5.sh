@@ -9,8 +9,8 @@ d=json.loads(sys.stdin.read()); print('$1', 'value %.5g ms %.5f rollout %.4g' % 
 {
 for rep in $(seq 1 ${REPS:-2}); do
   for cfg in ${CONFIGS:-2 3 4 5}; do
-    (cd _r05 && DMC_BENCH_NO_PMC=1 python bench.py --config $cfg --no-cpu-baseline --parity-steps 0 --pipeline 0 2>/dev/null | tail -1 | show "r05 cfg$cfg rep$rep")
-    DMC_BENCH_NO_PMC=1 python bench.py --config $cfg --no-cpu-baseline --parity-steps 0 --pipeline 0 --extra 0 2>/dev/null | tail -1 | show "r06 cfg$cfg rep$rep"
+    (cd _r05 && DMC_BENCH_NO_PMC=1 python bench.py --full --config $cfg --no-cpu-baseline --parity-steps 0 --pipeline 0 2>/dev/null | tail -1 | show "r05 cfg$cfg rep$rep")
+    DMC_BENCH_NO_PMC=1 python bench.py --full --config $cfg --no-cpu-baseline --parity-steps 0 --pipeline 0 --extra 0 2>/dev/null | tail -1 | show "r06 cfg$cfg rep$rep"
   done
 done
 } 2>&1 | tee gpurun_out/r06_ab_vs_round5.log

@@ -47,7 +47,7 @@ def run_all():
         env.pop('DMC_LIB_VARIANT', None)
         if v != '-':
           env['DMC_LIB_VARIANT'] = v
-        r = subprocess.run([sys.executable, 'bench.py', '--config', config, '--no-cpu-baseline', '--parity-steps', '0'],
+        r = subprocess.run([sys.executable, 'bench.py', '--full', '--config', config, '--no-cpu-baseline', '--parity-steps', '0'],
                            env=env, capture_output=True, text=True)
         if r.returncode:
           print('bench failed:', config, v, r.stderr[-300:], flush=True)

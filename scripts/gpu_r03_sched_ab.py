@@ -45,7 +45,7 @@ def tests(variant):
 
 
 def bench(config, variant, extra=()):
-  r = run([sys.executable, 'bench.py', '--config', str(config)] + list(extra), variant, 200)
+  r = run([sys.executable, 'bench.py', '--full', '--config', str(config)] + list(extra), variant, 200)
   if not r or r.returncode:
     print('bench failed', config, variant, (r.stderr[-800:] if r else 'timeout'), flush=True)
     return None

@@ -6,7 +6,7 @@ for c in 4 3; do
   for v in "" lpt16 lpt3; do
     echo "== config $c variant '${v:-main(alpha5)}'"
     for rep in 1 2; do
-      DMC_LIB_VARIANT=$v DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --config $c --no-cpu-baseline --parity-steps 0 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('rollout',{}))"
+      DMC_LIB_VARIANT=$v DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --full --config $c --no-cpu-baseline --parity-steps 0 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('rollout',{}))"
     done
     DMC_LIB_VARIANT=$v CONFIG=$c timeout 300 python scripts/occupancy_probe.py 2>&1 | python -c "
 import sys,json

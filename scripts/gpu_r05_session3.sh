@@ -15,13 +15,13 @@ timeout 900 python -m pytest tests/test_specialise.py tests/test_device_env.py -
 for cfg in 3 4 5; do
   for v in main nofloor noanchor; do
     if [ $v = main ]; then unset DMC_LIB_VARIANT; else export DMC_LIB_VARIANT=$v; fi
-    DMC_BENCH_NO_PMC=1 python bench.py --config $cfg --no-cpu-baseline 2>/dev/null | show "$v cfg$cfg"
+    DMC_BENCH_NO_PMC=1 python bench.py --full --config $cfg --no-cpu-baseline 2>/dev/null | show "$v cfg$cfg"
   done
 done 2>&1 | tee gpurun_out/r05_ab_variants.log
 unset DMC_LIB_VARIANT
 for cfg in 2 3 4 5; do
-  python bench.py --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "baked cfg$cfg"
-  DMC_NO_STATIC=1 DMC_SPECIALISE=cached python bench.py --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "plugin cfg$cfg"
-  DMC_NO_STATIC=1 DMC_SPECIALISE=0 python bench.py --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "generic cfg$cfg"
+  python bench.py --full --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "baked cfg$cfg"
+  DMC_NO_STATIC=1 DMC_SPECIALISE=cached python bench.py --full --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "plugin cfg$cfg"
+  DMC_NO_STATIC=1 DMC_SPECIALISE=0 python bench.py --full --config $cfg --no-cpu-baseline --parity-steps 0 2>/dev/null | show "generic cfg$cfg"
 done 2>&1 | tee gpurun_out/r05_generic_vs_static.log
 timeout 900 python scripts/device_env_runs.py > gpurun_out/r05_device_env_runs.log 2>&1; tail -4 gpurun_out/r05_device_env_runs.log

@@ -3,6 +3,7 @@
 # round-4 library with parity legs; specialise + device_env tests; the device environments' rates.
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out
+mkdir -p results      # bench.py's lines write here
 show() { python -c "
 import json,sys
 try:
@@ -13,7 +14,7 @@ try:
 except Exception as e: print('$1 FAILED', e)"; }
 timeout 900 python -m pytest tests/test_specialise.py tests/test_device_env.py -m gpu -q --timeout 600 -p no:cacheprovider > gpurun_out/r05_spec_devenv_tests.log 2>&1; echo "tests rc=$?"; tail -4 gpurun_out/r05_spec_devenv_tests.log
 for cfg in 2 3 4 5; do
-  DMC_LIB_VARIANT=r04 DMC_BENCH_NO_PMC=1 python bench.py --config $cfg --no-cpu-baseline 2>/dev/null | show "r04 cfg$cfg"
-  DMC_BENCH_NO_PMC=1 python bench.py --config $cfg --no-cpu-baseline 2>/dev/null | tee gpurun_out/r05_parity_final_cfg$cfg.json | show "new cfg$cfg"
+  DMC_LIB_VARIANT=r04 DMC_BENCH_NO_PMC=1 python bench.py --full --config $cfg --no-cpu-baseline 2>/dev/null | show "r04 cfg$cfg"
+  DMC_BENCH_NO_PMC=1 python bench.py --full --config $cfg --no-cpu-baseline 2>/dev/null | tee results/r05_parity_final_cfg$cfg.json | show "new cfg$cfg"
 done 2>&1 | tee gpurun_out/r05_ab_final_vs_round4.log
 timeout 900 python scripts/device_env_runs.py > gpurun_out/r05_device_env_runs.log 2>&1; tail -3 gpurun_out/r05_device_env_runs.log

@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_gpu_suite.py -m gpu -q -x -k "work_queue
 {
 for rep in 1 2 3; do for c in 4 3; do for v in xstat ""; do
   if [ -n "$v" ]; then export DMC_LIB_VARIANT=$v; else unset DMC_LIB_VARIANT; fi
-  DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --config $c --no-cpu-baseline --parity-steps 0 --pipeline 0 --extra 0 2>/dev/null | tail -1 | python -c "
+  DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --full --config $c --no-cpu-baseline --parity-steps 0 --pipeline 0 --extra 0 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('cfg $c %-12s value %.5g ms %.4f rollout %.5g' % ('static deal' if '$v' else 'bound at claim', d['value'], d['ms_per_step'], d['rollout']['value']))"
 done; done; done
 unset DMC_LIB_VARIANT

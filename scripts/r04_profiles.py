@@ -4,25 +4,27 @@ device environments, soak, wave tails, the host-buffer boundary, logs."""
 import csv, glob, json, os, shutil, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G, P = os.path.join(ROOT, 'gpurun_out'), os.path.join(ROOT, 'profiles')
+B = os.path.join(ROOT, 'results')      # the session's bench.py lines write there
+src = lambda f: os.path.join(B, f) if os.path.exists(os.path.join(B, f)) else os.path.join(G, f)
 PRE = os.environ.get('OUT_PREFIX', 'r04')      # a second session of the round is filed under another prefix (r04b)
 OUT = lambda f: os.path.join(P, f.replace('r04_', PRE + '_', 1))
 for f in ['r04_bench_cfg%d.json' % c for c in (2, 3, 4, 5)] + ['r04_bench_driver_cmd.json', 'r04_composer_runs.json', 'r04_soak_all_tasks.json',
          'r04_pcie_probe_cfg2.json', 'r04_gputests.log', 'r04_reference_on_hip.log'] + ['r04_wave_tail_cfg%d.json' % c for c in (2, 3, 4, 5)]:
-  if os.path.exists(os.path.join(G, f)):
-    shutil.copy(os.path.join(G, f), OUT(f))
+  if os.path.exists(src(f)):
+    shutil.copy(src(f), OUT(f))
 for c in (2, 3, 4, 5):
-  stats = glob.glob(os.path.join(G, 'r04_prof_cfg%d' % c, '**', '*kernel_stats.csv'), recursive=True)
+  stats = glob.glob(os.path.join(src('r04_prof_cfg%d' % c), '**', '*kernel_stats.csv'), recursive=True)
   if stats:
     shutil.copy(stats[0], OUT('r04_rocprof_kernel_stats_cfg%d.csv' % c))
   rows = []
-  for f in glob.glob(os.path.join(G, 'r04_prof_cfg%d' % c, '**', '*kernel_trace.csv'), recursive=True):
+  for f in glob.glob(os.path.join(src('r04_prof_cfg%d' % c), '**', '*kernel_trace.csv'), recursive=True):
     rows += [r for r in csv.DictReader(open(f)) if 'step_kernel' in r['Kernel_Name']]
   if not rows:
     continue
   rows.sort(key=lambda r: int(r['Start_Timestamp']))
   dur = [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3 for r in rows]
   try:
-    line = json.load(open(os.path.join(G, 'r04_prof_bench_cfg%d.json' % c)))
+    line = json.load(open(src('r04_prof_bench_cfg%d.json' % c)))
   except Exception:  # pylint: disable=broad-except
     line = {}
   K, W = line.get('steps'), line.get('warmup')

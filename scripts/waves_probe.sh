@@ -4,7 +4,7 @@
 # separates what the fifth environment brings from what the offload costs (profiles/r04_waves_probe_level3.log).
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 for w in ${WAVES:-5 4 3 5 4}; do
-  DMC_WAVES=$w DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --config 4 --no-cpu-baseline --parity-steps 0 2>/dev/null | python -c "
+  DMC_WAVES=$w DMC_BENCH_NO_PMC=1 timeout 300 python bench.py --full --config 4 --no-cpu-baseline --parity-steps 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('waves $w', 'value %.5g ms %.4f' % (d['value'], d['ms_per_step']), 'envs/CU', d['config']['info']['envs_per_cu'], 'grid', d['config']['info']['grid'])"
 done

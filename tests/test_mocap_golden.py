@@ -12,8 +12,8 @@ from dm_control_amd import mjcf_compiler as mc
 from dm_control_amd.suite import common
 from oracle.oracle import OraclePhysics
 
-from ref_root import REF  # noqa: E402
-REF_XML = REF + '/locomotion/walkers/assets/humanoid_CMU_V2019.xml'
+# byte copy of the reference's locomotion/walkers/assets/humanoid_CMU_V2019.xml
+REF_XML = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'humanoid_CMU_V2019.xml')
 
 
 def _check(model, root_joint, tol):
@@ -60,7 +60,6 @@ def test_oracle_kinematics_on_config4_model_match_mujoco_goldens():
   assert worst['xpos'] < 5e-15 and worst['xquat'] < 5e-15
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason='reference tree not present')
 def test_oracle_kinematics_on_unmodified_reference_walker_xml():
   """The same 20 poses through the reference's own humanoid_CMU_V2019.xml (free joint added the way
   composer attaches a walker: a `freejoint` on the root body)."""

@@ -16,8 +16,8 @@ from dm_control_amd.suite import common
 from emu_lib import EmuPhysics
 from oracle.oracle import OraclePhysics
 
-from ref_root import REF  # noqa: E402
-REF_XML = REF + '/mujoco/testing/assets/humanoid.xml'
+# byte copy of the reference's mujoco/testing/assets/humanoid.xml
+REF_XML = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'mujoco_testing_humanoid.xml')
 CT_FRICTION_DOF, CT_ELLIPTIC, CT_EQUALITY = 4, 3, 6
 
 
@@ -53,7 +53,6 @@ def _fallen_state(m, seed, steps=450):
   return p.qpos.copy(), p.qvel.copy(), p.qacc_warmstart.copy(), rs.uniform(-1, 1, mn.nu)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason='reference tree not present')
 def test_restated_asset_compiles_to_the_reference_blob():
   a = mc.compile_xml(open(REF_XML).read())
   b = mc.compile_xml(common.read_model('testing_humanoid_pgs.xml'))
