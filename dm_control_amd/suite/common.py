@@ -2,6 +2,8 @@ import os
 
 import numpy as np
 
+from dm_control_amd.suite.task_arrays import TaskArray
+
 _ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets')
 
 
@@ -33,16 +35,16 @@ def read_model(filename):
 
 
 def asarray(x, dtype=None):
-  """`np.asarray(x, dtype)` for the task code: numpy inputs take exactly that call; a device array (suite/device_env.TArr:
-  the same task code evaluated on GPU tensors) stays where it is."""
-  if type(x).__name__ in ('TArr', 'SArr'):
+  """`np.asarray(x, dtype)` for the task code: numpy inputs take exactly that call; a device array (a
+  suite/task_arrays.TaskArray: the same task code evaluated on GPU tensors, or traced) stays where it is."""
+  if isinstance(x, TaskArray):
     return x.astype(dtype) if dtype is not None else x
   return np.asarray(x) if dtype is None else np.asarray(x, dtype=dtype)
 
 
 def array_copy(x, dtype=None):
   """`np.array(x, dtype, copy=True)` likewise."""
-  if type(x).__name__ in ('TArr', 'SArr'):
+  if isinstance(x, TaskArray):
     y = x.copy()
     return y.astype(dtype) if dtype is not None else y
   return np.array(x, copy=True) if dtype is None else np.array(x, dtype=dtype, copy=True)

@@ -25,11 +25,15 @@ physics (targets ...) in place.
 torch is plumbing here (memory + elementwise ops); the physics is the fused HIP kernel.
 """
 import collections
+import operator
 
 import numpy as np
 
+from dm_control_amd.suite import task_arrays
+from dm_control_amd.suite.task_arrays import TaskArray
 
-class TArr:
+
+class TArr(TaskArray):
   """A torch tensor that numpy code can compute with (see the module docstring).  Batch-first shapes, like the facade's
   batched arrays."""
 
@@ -116,45 +120,17 @@ class TArr:
   def __setitem__(self, key, value):
     self.t[self._key(key)] = _tensor(value, self.t)
 
-  # -- arithmetic ------------------------------------------------------------------------------------------------------
-  def _bin(self, other, fn, reverse=False):
-    o = _tensor(other, self.t)
+  # -- arithmetic (the operators: task_arrays.TaskArray) --------------------------------------------------------------
+  def _bin(self, key, other, reverse=False):
+    fn, o = _BIN[key], _tensor(other, self.t)
     return TArr(fn(o, self.t) if reverse else fn(self.t, o))
 
-  def __add__(self, o): return self._bin(o, lambda a, b: a + b)
-  def __radd__(self, o): return self._bin(o, lambda a, b: a + b, True)
-  def __sub__(self, o): return self._bin(o, lambda a, b: a - b)
-  def __rsub__(self, o): return self._bin(o, lambda a, b: a - b, True)
-  def __mul__(self, o): return self._bin(o, lambda a, b: a * b)
-  def __rmul__(self, o): return self._bin(o, lambda a, b: a * b, True)
-  def __truediv__(self, o): return self._bin(o, lambda a, b: a / b)
-  def __rtruediv__(self, o): return self._bin(o, lambda a, b: a / b, True)
-  def __pow__(self, o): return self._bin(o, lambda a, b: a ** b)
-  def __rpow__(self, o): return self._bin(o, lambda a, b: a ** b, True)
-  def __lt__(self, o): return self._bin(o, lambda a, b: a < b)
-  def __le__(self, o): return self._bin(o, lambda a, b: a <= b)
-  def __gt__(self, o): return self._bin(o, lambda a, b: a > b)
-  def __ge__(self, o): return self._bin(o, lambda a, b: a >= b)
-  def __eq__(self, o): return self._bin(o, lambda a, b: a == b)
-  def __ne__(self, o): return self._bin(o, lambda a, b: a != b)
-  def __and__(self, o): return self._bin(o, lambda a, b: a & b)
-  def __rand__(self, o): return self._bin(o, lambda a, b: a & b, True)
-  def __or__(self, o): return self._bin(o, lambda a, b: a | b)
-  def __ror__(self, o): return self._bin(o, lambda a, b: a | b, True)
-  def __invert__(self): return TArr(~self.t)
-  def __neg__(self): return TArr(-self.t)
-  def __pos__(self): return self
-  def __abs__(self): return TArr(self.t.abs())
-  __hash__ = None
+  def _un(self, key):
+    return TArr(_UN[key](self.t))
 
   # -- methods numpy code calls on arrays ----------------------------------------------------------------------------
-  def reshape(self, *shape):
-    if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
-      shape = tuple(shape[0])
-    return TArr(self.t.reshape(tuple(int(s) for s in shape)))
-
-  def ravel(self):
-    return TArr(self.t.reshape(-1))
+  def _reshape(self, shape):
+    return TArr(self.t.reshape(shape))
 
   def copy(self):
     return TArr(self.t.clone())
@@ -166,37 +142,33 @@ class TArr:
   def squeeze(self, axis=None):
     return TArr(self.t.squeeze() if axis is None else self.t.squeeze(axis))
 
-  def dot(self, other):
-    o = _tensor(other, self.t)
-    return TArr(self.t @ o)
+  @staticmethod
+  def _dot(a, b):
+    ref = _first((a, b))
+    return TArr(_tensor(a, ref) @ _tensor(b, ref))
 
-  def clip(self, lo=None, hi=None):
-    return TArr(self.t.clamp(lo, hi))
+  @staticmethod
+  def _clip(x, lo=None, hi=None, **k):
+    return TArr(x.t.clamp(lo, hi))
 
-  def sum(self, axis=None, keepdims=False): return _reduce('sum', self, axis, keepdims)
-  def mean(self, axis=None, keepdims=False): return _reduce('mean', self, axis, keepdims)
-  def prod(self, axis=None, keepdims=False): return _reduce('prod', self, axis, keepdims)
-  def min(self, axis=None, keepdims=False): return _reduce('amin', self, axis, keepdims)
-  def max(self, axis=None, keepdims=False): return _reduce('amax', self, axis, keepdims)
-  def all(self, axis=None, keepdims=False): return _reduce('all', self, axis, keepdims)
-  def any(self, axis=None, keepdims=False): return _reduce('any', self, axis, keepdims)
+  @staticmethod
+  def _reduce(key, x, axis, keepdims):
+    return _torch_reduce(_REDUCE[key], x, axis, keepdims)
 
-  # -- numpy dispatch ---------------------------------------------------------------------------------------------------
-  def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
-    if method != '__call__' or kwargs.get('out') is not None:
-      return NotImplemented
-    fn = _UFUNCS.get(ufunc.__name__)
+  # -- numpy dispatch (the protocols: task_arrays.TaskArray) -----------------------------------------------------------
+  def _ufunc(self, name, inputs):
+    fn = _UFUNCS.get(name)
     if fn is None:
       return NotImplemented
     ref = next(x.t for x in inputs if isinstance(x, TArr))
     return TArr(fn(*[_tensor(x, ref) for x in inputs]))
 
-  def __array_function__(self, func, types, args, kwargs):
-    fn = _FUNCS.get(func)
-    if fn is None:
-      return NotImplemented
-    return fn(*args, **kwargs)
 
+_BIN = {'add': operator.add, 'sub': operator.sub, 'mul': operator.mul, 'div': operator.truediv, 'pow': operator.pow,
+        'lt': operator.lt, 'le': operator.le, 'gt': operator.gt, 'ge': operator.ge, 'eq': operator.eq, 'ne': operator.ne,
+        'and': operator.and_, 'or': operator.or_}
+_UN = {'not': operator.invert, 'neg': operator.neg, 'abs': operator.abs}
+_REDUCE = {'sum': 'sum', 'mean': 'mean', 'prod': 'prod', 'min': 'amin', 'max': 'amax', 'all': 'all', 'any': 'any'}      # torch's names
 
 _CONST = {}      # host constants that reached a torch op (index arrays, model scalars, targets): one device copy each
 
@@ -259,7 +231,7 @@ def _scalar(x, fl, device):
   return t
 
 
-def _reduce(name, x, axis, keepdims):
+def _torch_reduce(name, x, axis, keepdims):
   import torch
   t = x.t if isinstance(x, TArr) else x
   if axis is None:
@@ -348,35 +320,21 @@ def _build_tables():
   for k in ('maximum', 'minimum', 'arctan2', 'logical_and', 'logical_or', 'hypot', 'power', 'add', 'subtract', 'multiply', 'true_divide',
             'divide', 'less', 'less_equal', 'greater', 'greater_equal', 'equal', 'not_equal'):
     u[k] = lift(u[k])
-  f = {
+  f = task_arrays.shared_functions(TArr)
+  f.update({
       np.concatenate: _cat(torch.cat), np.stack: _cat(torch.stack), np.where: _where, np.linalg.norm: _norm, np.einsum: _einsum,
-      np.sum: lambda x, axis=None, keepdims=False, **k: _reduce('sum', x, axis, keepdims),
-      np.mean: lambda x, axis=None, keepdims=False, **k: _reduce('mean', x, axis, keepdims),
-      np.prod: lambda x, axis=None, keepdims=False, **k: _reduce('prod', x, axis, keepdims),
-      np.min: lambda x, axis=None, keepdims=False, **k: _reduce('amin', x, axis, keepdims),
-      np.max: lambda x, axis=None, keepdims=False, **k: _reduce('amax', x, axis, keepdims),
-      np.amin: lambda x, axis=None, keepdims=False, **k: _reduce('amin', x, axis, keepdims),
-      np.amax: lambda x, axis=None, keepdims=False, **k: _reduce('amax', x, axis, keepdims),
-      np.all: lambda x, axis=None, keepdims=False, **k: _reduce('all', x, axis, keepdims),
-      np.any: lambda x, axis=None, keepdims=False, **k: _reduce('any', x, axis, keepdims),
-      np.clip: lambda x, lo=None, hi=None, **k: TArr(x.t.clamp(lo, hi)),
-      np.shape: lambda x: x.shape, np.ndim: lambda x: x.ndim, np.size: lambda x: x.size,
-      np.reshape: lambda x, shape, **k: x.reshape(shape), np.ravel: lambda x, **k: x.ravel(),
-      np.squeeze: lambda x, axis=None: x.squeeze(axis),
       np.expand_dims: lambda x, axis: TArr(x.t.unsqueeze(axis)),
       np.broadcast_to: lambda x, shape, **k: TArr(torch.broadcast_to(x.t, tuple(shape))),
       np.zeros_like: lambda x, dtype=None, **k: TArr(torch.zeros_like(x.t, dtype=_torch_dtype(dtype) if dtype else None)),
       np.ones_like: lambda x, dtype=None, **k: TArr(torch.ones_like(x.t, dtype=_torch_dtype(dtype) if dtype else None)),
-      np.copy: lambda x, **k: x.copy(),
-      np.dot: lambda a, b: TArr(_tensor(a, _first((a, b))) @ _tensor(b, _first((a, b)))),
-      np.atleast_1d: lambda x: x if x.ndim else x.reshape(1),
       np.cross: lambda a, b, **k: TArr(torch.linalg.cross(_tensor(a, _first((a, b))), _tensor(b, _first((a, b))), dim=k.get('axis', -1))),
       np.transpose: lambda x, axes=None: TArr(x.t.permute(*axes) if axes else x.t.T),
-  }
+  })
   return u, f
 
 
-_UFUNCS, _FUNCS = {}, {}
+_UFUNCS, _FUNCS = {}, {}      # (filled at the first environment: the tables need torch)
+TArr._FUNCS = _FUNCS
 
 
 def _ensure_tables():
@@ -386,163 +344,53 @@ def _ensure_tables():
     _FUNCS.update(f)
 
 
-def asarray(x, dtype=None):
-  """`np.asarray(x, dtype)` for the task ports: numpy arrays take exactly that call; a TArr stays on the device."""
-  if isinstance(x, TArr):
-    return x.astype(dtype) if dtype is not None else x
-  return np.asarray(x) if dtype is None else np.asarray(x, dtype=dtype)
-
-
-def array_copy(x, dtype=None):
-  """`np.array(x, dtype, copy=True)` likewise."""
-  if isinstance(x, TArr):
-    y = x.copy()
-    return y.astype(dtype) if dtype is not None else y
-  return np.array(x, copy=True) if dtype is None else np.array(x, dtype=dtype, copy=True)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # the view: the domain's Physics subclass over device tensors
 # ---------------------------------------------------------------------------------------------------------------------
-class _DevData:
+def _episode_tensor(view, name, val):
+  """The device copy of a per-episode array the task hung on the physics (targets ...), refreshed IN PLACE at every
+  restart: a captured graph keeps reading the same memory."""
+  import torch
+  cache = view.__dict__['_episode']
+  ent = cache.get(name)
+  if ent is None or ent[0].shape != val.shape:
+    ent = [torch.as_tensor(val, device=view._device).to(view._dtype), view._epoch]
+    cache[name] = ent
+  elif ent[1] != view._epoch:
+    ent[0].copy_(torch.as_tensor(val, device=view._device).to(view._dtype))
+    ent[1] = view._epoch
+  return TArr(ent[0])
 
-  def __init__(self, view):
-    object.__setattr__(self, '_v', view)
 
-  def __getattr__(self, name):
-    v = self._v
-    t = v._tensors.get(name)
-    if t is None:
-      raise AttributeError('data.%s is not served on the device (bound fields: %s)' % (name, sorted(v._tensors)))
-    return v._as_batched(name, t)
-
-  def __setattr__(self, name, value):
-    raise AttributeError('the device view is read-only: states are written through the facade at episode start')
+def _mirror(view, name, val):
+  return _episode_tensor(view, name, val) if task_arrays.is_episode_array(val, view.batch_size) else val
 
 
 def _make_view_class(cls):
-  from dm_control_amd import physics as facade
-
-  class DeviceView(cls):
-    """`cls` (a suite domain's Physics) with `data` / `named.data` served from the batch's bound device tensors."""
-
-    def __init__(self):      # pylint: disable=super-init-not-called
-      raise TypeError('built by GenericDeviceEnv')
-
-    def __getattr__(self, name):
-      # whatever the task hung on the physics at episode start (targets ...): the host facade's value, as a device copy
-      # that is refreshed IN PLACE at every restart (a captured graph keeps reading the same memory)
-      if name.startswith('_'):
-        raise AttributeError(name)
-      host = self.__dict__['_host']
-      if name in host.__dict__ or hasattr(type(host), name):
-        val = getattr(host, name)
-        if isinstance(val, np.ndarray) and val.ndim >= 1 and val.dtype.kind == 'f' and (val.shape[0] == self.batch_size or self.batch_size == 1):
-          return self._episode_tensor(name, val)
-        return val
-      raise AttributeError(name)
-
-    def _episode_tensor(self, name, val):
-      import torch
-      cache = self.__dict__['_episode']
-      ent = cache.get(name)
-      if ent is None or ent[0].shape != val.shape:
-        ent = [torch.as_tensor(val, device=self._device).to(self._dtype), self._epoch]
-        cache[name] = ent
-      elif ent[1] != self._epoch:
-        ent[0].copy_(torch.as_tensor(val, device=self._device).to(self._dtype))
-        ent[1] = self._epoch
-      return TArr(ent[0])
-
-    def _as_batched(self, name, t):
-      B = self.batch_size
-      ncol = facade._FIELD_AXES.get(name, (None, None))[1]      # pylint: disable=protected-access
-      if name in ('time', 'ncon', 'nefc', 'solver_iter'):
-        return TArr(t[0])
-      if ncol:
-        return TArr(t.T.reshape(B, t.shape[0] // ncol, ncol))
-      return TArr(t.T)
-
-    # engine.py:589-622 accessors: copies in the reference, fresh tensors here
-    def control(self): return self.data.ctrl.copy()
-    def position(self): return self.data.qpos.copy()
-    def velocity(self): return self.data.qvel.copy()
-    def activation(self): return self.data.act.copy()
-    def state(self): return self.get_state()
-    def time(self): return self.data.time
-    def timestep(self): return self.model.opt.timestep
-
-    def get_state(self, sig=None):
-      if sig is not None:
-        raise NotImplementedError('state signatures are served by the facade')
-      parts = [self.data.qpos, self.data.qvel] + ([self.data.act] if self.model.na else [])
-      return np.concatenate(parts, axis=-1)
-
-    def step(self, *a, **k): raise TypeError('the device view does not step: GenericDeviceEnv.step does')
-    forward = reset = after_reset = set_control = step
-
-    def free(self):
-      pass
-
-    def __del__(self):
-      pass
-  DeviceView.__name__ = 'Device' + cls.__name__
-  return DeviceView
+  """`cls` (a suite domain's Physics) with `data` / `named.data` served from the batch's bound device tensors (rows, B),
+  batch first."""
+  return task_arrays.make_view_class(
+      cls, 'Device', leaf=lambda view, name, t: TArr(t.T), host_attr=_mirror, built_by='GenericDeviceEnv',
+      read_only='the device view is read-only: states are written through the facade at episode start',
+      no_step='the device view does not step: GenericDeviceEnv.step does')
 
 
-class GenericDeviceEnv:
+class GenericDeviceEnv(task_arrays.TaskEnv):
   """B environments of `suite.<domain>.<task>` resident on one GPU; `step(action)` -> (obs (B, n), reward (B,), done
   (B,)) device tensors.  See the module docstring."""
 
   def __init__(self, domain, task, batch_size, precision=32, device_id=0, seed=0, capture=True, task_kwargs=None,
                termination_check_every=25, copy_outputs=True, _device='cuda'):
-    import torch
-    from dm_control_amd import physics as facade
-    from dm_control_amd import suite
     _ensure_tables()
-    self.torch = torch
-    self.B = int(batch_size)
-    self.device = torch.device(_device, device_id) if _device == 'cuda' else torch.device('cpu')
-    self.dtype = torch.float32 if precision == 32 else torch.float64
-    kw = dict(task_kwargs or {})
-    kw.setdefault('random', seed)
-    self.host_env = suite.load(domain, task, task_kwargs=kw, physics_kwargs=dict(batch_size=self.B, precision=precision, device_id=device_id))
-    p = self.host_env.physics
-    self.host_physics, self.task, self.model = p, self.host_env.task, p.model
-    self.n_sub_steps = int(self.host_env._n_sub_steps)      # pylint: disable=protected-access
-    lim = self.host_env._step_limit      # pylint: disable=protected-access
+    lim = self._load_host(domain, task, batch_size, precision, device_id, seed, task_kwargs, device=_device)
     self.step_limit = None if lim == float('inf') else float(lim)      # (control.Environment: done when count >= limit)
-    # bind every field the facade serves from the device to a torch tensor (zero copy)
-    self._tensors = {}
-    names = [n for n in facade._FIELD_AXES if n not in ('xanchor', 'xaxis', 'ten_length', 'ten_velocity')]      # pylint: disable=protected-access
-    for name in names + ['time', 'ncon']:
-      try:
-        r = p.batch._rows      # pylint: disable=protected-access
-        rows, is_int = r(name) if callable(r) else (r[name] if name in r else int(np.asarray(p.batch.get(name)).shape[1]), name in ('ncon', 'nefc', 'solver_iter'))
-      except Exception:      # pylint: disable=broad-except
-        continue
-      dt = torch.float64 if name == 'time' else torch.int32 if is_int else self.dtype
-      t = torch.zeros((max(rows, 1), self.B), dtype=dt, device=self.device)
-      if rows:
-        cur = p.batch.get(name)
-        t.copy_(torch.as_tensor(np.ascontiguousarray(np.asarray(cur).T), device=self.device).to(dt))
-        if self.device.type == 'cuda':
-          p.batch.bind(name, t.data_ptr())
-      self._tensors[name] = t if rows else t[:0]
-    View = _make_view_class(type(p))
-    v = object.__new__(View)
-    v.__dict__.update(_host=p, _episode={}, _epoch=0, _tensors=self._tensors, _device=self.device, _dtype=self.dtype,
+    # every field the facade serves from the device, bound to a torch tensor (zero copy)
+    self._bind_fields(task_arrays.served_fields(), mirror=True)
+    p = self.host_physics
+    v = object.__new__(_make_view_class(type(p)))
+    v.__dict__.update(_host=p, _episode={}, _epoch=0, _fields=self._tensors, _device=self.device, _dtype=self.dtype,
                       model=p.model, batch_size=self.B)
-    v.__dict__['data'] = _DevData(v)
-    named = facade._Named()      # pylint: disable=protected-access
-    named.model = p.named.model
-    named.data = facade._Named()      # pylint: disable=protected-access
-    axes = facade._make_axes(p.model)      # pylint: disable=protected-access
-    for field, (rowkind, ncol) in facade._FIELD_AXES.items():      # pylint: disable=protected-access
-      if field in self._tensors:
-        cols = facade._Axis(facade._COLS[ncol]) if ncol else None      # pylint: disable=protected-access
-        setattr(named.data, field, facade.FieldIndexer(lambda f=field: getattr(v.data, f), axes[rowkind], cols, True))
-    v.__dict__['named'] = named
+    task_arrays.build_named(v, p, self._tensors, True)
     self.view = v
     self.ctrl = self._tensors['ctrl']
     self.steps = 0
@@ -580,16 +428,9 @@ class GenericDeviceEnv:
     v.__dict__['_epoch'] += 1
     # what the task hung on the physics (targets, radii ...): mirrored onto the view -- instance attributes, because the
     # domain classes declare them as class attributes (`target_xy = None`) that a plain lookup would find first; arrays
-    # with a leading batch axis become device tensors that every restart rewrites IN PLACE
-    for k, val in vars(p).items():
-      if k.startswith('_') or k in ('model', 'batch', 'data', 'named', 'batch_size', 'legacy_step'):
-        continue
-      # (B == 1: the ports drop the batch axis -- `xy[0] if B == 1 else xy` -- so ANY float array is per-episode data that
-      # must be refreshed in place: as a host array it would be baked into the captured graph at its first value)
-      if isinstance(val, np.ndarray) and val.ndim >= 1 and val.dtype.kind == 'f' and (val.shape[0] == self.B or self.B == 1):
-        v.__dict__[k] = v._episode_tensor(k, val)
-      else:
-        v.__dict__[k] = val
+    # with a leading batch axis (task_arrays.is_episode_array) become device tensors that every restart rewrites IN PLACE
+    for k, val in task_arrays.task_attrs(p):
+      v.__dict__[k] = _mirror(v, k, val)
     self.steps = 0
     return self.observation()
 
@@ -607,9 +448,6 @@ class GenericDeviceEnv:
     if isinstance(r, TArr):
       return r.t.to(self.dtype).reshape(self.B)
     return self.torch.full((self.B,), float(r), dtype=self.dtype, device=self.device)
-
-  def _stream(self):
-    return self.torch.cuda.current_stream().cuda_stream if self.device.type == 'cuda' else None
 
   def _pull(self):
     """CPU harness only (tests: torch CPU tensors next to the oracle stand-in, which has nothing to bind): the tensors
@@ -637,20 +475,14 @@ class GenericDeviceEnv:
       getattr(self.host_physics.batch, 'wait_specialised', lambda: None)()      # (a graph keeps the kernel it was captured with)
       self._g_action = action.clone()
       state = [self._tensors[n] for n in ('qpos', 'qvel', 'qacc_warmstart', 'time', 'ctrl', 'act') if n in self._tensors]
-      saved = [t.clone() for t in state]
-      side = torch.cuda.Stream()
-      side.wait_stream(torch.cuda.current_stream())
-      with torch.cuda.stream(side):              # warm-up off the default stream, as graph capture requires; it also fills
-        self._control_step(self._g_action)       # the cache of device constants (_const), so that the capture run uploads nothing
-      torch.cuda.current_stream().wait_stream(side)
-      reads = TArr.host_reads
-      graph = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(graph):
-        self._g_out = self._control_step(self._g_action)
-      if TArr.host_reads != reads:
+      reads = []
+
+      def run():      # (the warm-up run also fills the cache of device constants, _const: the capture run uploads nothing)
+        reads[:] = [TArr.host_reads]
+        return self._control_step(self._g_action)
+      graph, self._g_out = task_arrays.capture_step(torch, run, state)
+      if TArr.host_reads != reads[0]:
         raise RuntimeError('the task layer read the device during capture')
-      for t, v in zip(state, saved):             # the warm-up step is taken back: the replay below is this call's step
-        t.copy_(v)
       self._graph = graph
     self._g_action.copy_(action)
     self._graph.replay()
@@ -679,13 +511,9 @@ class GenericDeviceEnv:
       obs = self.reset()
     return obs, rew, flags
 
-  def warnings(self):
-    return self.host_physics.batch.get('warning')
-
   def close(self):
-    self._graph = None
     self._consts = {}
-    self.host_physics.free()
+    super().close()
 
 
 def _base_termination():

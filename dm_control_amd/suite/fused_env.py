@@ -39,6 +39,9 @@ import subprocess
 
 import numpy as np
 
+from dm_control_amd.suite import task_arrays
+from dm_control_amd.suite.task_arrays import TaskArray, episode_attrs, field_rows, served_fields
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -239,11 +242,10 @@ def _elementwise(fn, *xs):
   return SArr(out)
 
 
-class SArr:
+class SArr(TaskArray):
   """numpy-compatible array of expression nodes (single-environment shapes; the batch is the kernel's thread index)."""
 
   __array_priority__ = 2000
-  __hash__ = None
 
   def __init__(self, a):
     if not isinstance(a, np.ndarray):
@@ -279,59 +281,26 @@ class SArr:
   def __setitem__(self, key, value):
     self.a[key] = _obj(value)
 
-  def _bin(self, op, o, rev=False):
+  def _bin(self, op, o, rev=False):      # (the operators: task_arrays.TaskArray; its keys are Graph.binary's ops)
     g = _g()
     return _elementwise((lambda p, q: g.binary(op, q, p)) if rev else (lambda p, q: g.binary(op, p, q)), self, o)
 
-  def __add__(self, o): return self._bin('add', o)
-  def __radd__(self, o): return self._bin('add', o, True)
-  def __sub__(self, o): return self._bin('sub', o)
-  def __rsub__(self, o): return self._bin('sub', o, True)
-  def __mul__(self, o): return self._bin('mul', o)
-  def __rmul__(self, o): return self._bin('mul', o, True)
-  def __truediv__(self, o): return self._bin('div', o)
-  def __rtruediv__(self, o): return self._bin('div', o, True)
-  def __pow__(self, o): return self._bin('pow', o)
-  def __rpow__(self, o): return self._bin('pow', o, True)
-  def __lt__(self, o): return self._bin('lt', o)
-  def __le__(self, o): return self._bin('le', o)
-  def __gt__(self, o): return self._bin('gt', o)
-  def __ge__(self, o): return self._bin('ge', o)
-  def __eq__(self, o): return self._bin('eq', o)
-  def __ne__(self, o): return self._bin('ne', o)
-  def __and__(self, o): return self._bin('and', o)
-  def __rand__(self, o): return self._bin('and', o, True)
-  def __or__(self, o): return self._bin('or', o)
-  def __ror__(self, o): return self._bin('or', o, True)
-  def __invert__(self): return _elementwise(lambda p: _g().unary('not', p), self)
-  def __neg__(self): return _elementwise(lambda p: _g().unary('neg', p), self)
-  def __pos__(self): return self
-  def __abs__(self): return _elementwise(lambda p: _g().unary('abs', p), self)
+  def _un(self, op):
+    return _elementwise(lambda p: _g().unary(op, p), self)
 
-  def reshape(self, *shape):
-    if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
-      shape = tuple(shape[0])
-    return SArr(self.a.reshape(tuple(int(s) for s in shape)))
+  def _reshape(self, shape):
+    return SArr(self.a.reshape(shape))
 
-  def ravel(self): return SArr(self.a.reshape(-1))
   def flatten(self): return SArr(self.a.reshape(-1).copy())
   def copy(self): return SArr(self.a.copy())
   def astype(self, dtype, copy=True): return self
   def squeeze(self, axis=None): return SArr(self.a.squeeze() if axis is None else self.a.squeeze(axis))
-  def dot(self, other): return _dot(self, other)
-  def clip(self, lo=None, hi=None): return _clip(self, lo, hi)
-  def sum(self, axis=None, keepdims=False): return _reduce('add', self, axis, keepdims)
-  def mean(self, axis=None, keepdims=False): return _mean(self, axis, keepdims)
-  def prod(self, axis=None, keepdims=False): return _reduce('mul', self, axis, keepdims)
-  def min(self, axis=None, keepdims=False): return _reduce('min', self, axis, keepdims)
-  def max(self, axis=None, keepdims=False): return _reduce('max', self, axis, keepdims)
-  def all(self, axis=None, keepdims=False): return _reduce('and', self, axis, keepdims)
-  def any(self, axis=None, keepdims=False): return _reduce('or', self, axis, keepdims)
 
-  def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
-    if method != '__call__' or kwargs.get('out') is not None:
-      return NotImplemented
-    name = ufunc.__name__
+  @staticmethod
+  def _reduce(key, x, axis, keepdims):
+    return _mean(x, axis, keepdims) if key == 'mean' else _fold(_REDUCE[key], x, axis, keepdims)
+
+  def _ufunc(self, name, inputs):
     g = _g()
     if name in _UFUNC_UNARY:
       op = _UFUNC_UNARY[name]
@@ -349,13 +318,8 @@ class SArr:
       return _elementwise(lambda p: g.binary('ne', p, p), inputs[0])
     return NotImplemented
 
-  def __array_function__(self, func, types, args, kwargs):
-    fn = _FUNCS.get(func)
-    if fn is None:
-      return NotImplemented
-    return fn(*args, **kwargs)
 
-
+_REDUCE = {'sum': 'add', 'prod': 'mul', 'min': 'min', 'max': 'max', 'all': 'and', 'any': 'or'}      # Graph.binary's ops
 _UFUNC_UNARY = {'negative': 'neg', 'absolute': 'abs', 'fabs': 'abs', 'sqrt': 'sqrt', 'exp': 'exp', 'log': 'log', 'log1p': 'log1p',
                 'sin': 'sin', 'cos': 'cos', 'tan': 'tan', 'arcsin': 'arcsin', 'arccos': 'arccos', 'arctan': 'arctan',
                 'sinh': 'sinh', 'cosh': 'cosh', 'tanh': 'tanh', 'arccosh': 'arccosh', 'arctanh': 'arctanh', 'arcsinh': 'arcsinh',
@@ -367,7 +331,7 @@ _UFUNC_BINARY = {'add': 'add', 'subtract': 'sub', 'multiply': 'mul', 'true_divid
                  'logical_or': 'or'}
 
 
-def _reduce(op, x, axis, keepdims):
+def _fold(op, x, axis, keepdims):
   g = _g()
   a = _obj(x)
   if a.size == 0:
@@ -393,7 +357,7 @@ def _mean(x, axis=None, keepdims=False):
   else:
     axes = tuple(axis) if isinstance(axis, (tuple, list)) else (int(axis),)
     n = int(np.prod([a.shape[ax] for ax in axes]))
-  return _reduce('add', x, axis, keepdims) / float(n)
+  return _fold('add', x, axis, keepdims) / float(n)
 
 
 def _clip(x, lo=None, hi=None, **k):
@@ -416,7 +380,7 @@ def _norm(x, ord=None, axis=None, keepdims=False):
     raise NotImplementedError('fused_env: np.linalg.norm with ord=%r' % (ord,))
   g = _g()
   sq = x * x
-  s = _reduce('add', sq, axis, keepdims)
+  s = _fold('add', sq, axis, keepdims)
   return _elementwise(lambda p: g.unary('sqrt', p), s)
 
 
@@ -483,110 +447,36 @@ def _cross(a, b, **k):
   return SArr(np.stack([(ay * bz - az * by).a, (az * bx - ax * bz).a, (ax * by - ay * bx).a], axis=-1))
 
 
-_FUNCS = {
+SArr._dot, SArr._clip = staticmethod(_dot), staticmethod(_clip)
+SArr._FUNCS = _FUNCS = task_arrays.shared_functions(SArr)
+_FUNCS.update({
     np.concatenate: _cat(np.concatenate), np.stack: _cat(np.stack), np.hstack: lambda arrays: _cat(np.concatenate)([np.atleast_1d(_obj(a)) for a in arrays], axis=-1),
-    np.where: _where, np.linalg.norm: _norm, np.einsum: _einsum, np.dot: _dot, np.clip: _clip, np.cross: _cross,
-    np.sum: lambda x, axis=None, keepdims=False, **k: _reduce('add', x, axis, keepdims),
-    np.mean: lambda x, axis=None, keepdims=False, **k: _mean(x, axis, keepdims),
-    np.prod: lambda x, axis=None, keepdims=False, **k: _reduce('mul', x, axis, keepdims),
-    np.min: lambda x, axis=None, keepdims=False, **k: _reduce('min', x, axis, keepdims),
-    np.max: lambda x, axis=None, keepdims=False, **k: _reduce('max', x, axis, keepdims),
-    np.amin: lambda x, axis=None, keepdims=False, **k: _reduce('min', x, axis, keepdims),
-    np.amax: lambda x, axis=None, keepdims=False, **k: _reduce('max', x, axis, keepdims),
-    np.all: lambda x, axis=None, keepdims=False, **k: _reduce('and', x, axis, keepdims),
-    np.any: lambda x, axis=None, keepdims=False, **k: _reduce('or', x, axis, keepdims),
-    np.shape: lambda x: x.shape, np.ndim: lambda x: x.ndim, np.size: lambda x: x.size,
-    np.reshape: lambda x, shape, **k: x.reshape(shape), np.ravel: lambda x, **k: x.ravel(),
-    np.squeeze: lambda x, axis=None: x.squeeze(axis), np.expand_dims: lambda x, axis: SArr(np.expand_dims(x.a, axis)),
+    np.where: _where, np.linalg.norm: _norm, np.einsum: _einsum, np.cross: _cross,
+    np.expand_dims: lambda x, axis: SArr(np.expand_dims(x.a, axis)),
     np.broadcast_to: lambda x, shape, **k: SArr(np.broadcast_to(x.a, tuple(shape))),
     np.zeros_like: lambda x, dtype=None, **k: np.zeros(x.shape), np.ones_like: lambda x, dtype=None, **k: np.ones(x.shape),
-    np.copy: lambda x, **k: x.copy(), np.atleast_1d: lambda x: x if x.ndim else x.reshape(1),
     np.transpose: lambda x, axes=None: SArr(np.transpose(x.a, axes)),
     np.isscalar: lambda x: False,
-}
+})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the symbolic view: the domain's Physics subclass, one environment, expression leaves instead of numbers
 # ---------------------------------------------------------------------------------------------------------------------
-class _SymData:
-
-  def __init__(self, view):
-    object.__setattr__(self, '_v', view)
-
-  def __getattr__(self, name):
-    v = self._v
-    rows = v._rows.get(name)
-    if rows is None:
-      raise AttributeError('data.%s is not served on the device (bound fields: %s)' % (name, sorted(v._rows)))
-    return v._leaf_array(name, rows)
-
-  def __setattr__(self, name, value):
-    raise AttributeError('the symbolic view is read-only')
+def _leaves(view, name, rows):
+  g = _g()
+  kind = 'i' if name in task_arrays.INT_FIELDS else 'f'
+  a = np.empty(rows, dtype=object)
+  for k in range(rows):
+    a[k] = g.load(name, k, kind)
+  return SArr(a)
 
 
 def _make_sym_view_class(cls):
-  from dm_control_amd import physics as facade
-
-  class SymView(cls):
-    """`cls` (a suite domain's Physics) at batch size 1 whose `data` arrays are SArr leaves."""
-
-    def __init__(self):      # pylint: disable=super-init-not-called
-      raise TypeError('built by FusedDeviceEnv')
-
-    def __getattr__(self, name):
-      if name.startswith('_'):
-        raise AttributeError(name)
-      host = self.__dict__['_host']
-      attrs = self.__dict__['_attrs']
-      if name in attrs:
-        width, shape = attrs[name]
-        g = _g()
-        a = np.empty(width, dtype=object)
-        for j in range(width):
-          a[j] = g.attr(name, j, width)
-        return SArr(a.reshape(shape))
-      if name in host.__dict__ or hasattr(type(host), name):
-        return getattr(host, name)
-      raise AttributeError(name)
-
-    def _leaf_array(self, name, rows):
-      g = _g()
-      kind = 'i' if name in ('ncon', 'nefc', 'solver_iter') else 'f'
-      a = np.empty(max(rows, 0), dtype=object)
-      for k in range(rows):
-        a[k] = g.load(name, k, kind)
-      ncol = facade._FIELD_AXES.get(name, (None, None))[1]      # pylint: disable=protected-access
-      if name in ('time', 'ncon', 'nefc', 'solver_iter'):
-        return SArr(a[0])
-      if ncol:
-        return SArr(a.reshape(rows // ncol, ncol))
-      return SArr(a)
-
-    def control(self): return self.data.ctrl.copy()
-    def position(self): return self.data.qpos.copy()
-    def velocity(self): return self.data.qvel.copy()
-    def activation(self): return self.data.act.copy()
-    def state(self): return self.get_state()
-    def time(self): return self.data.time
-    def timestep(self): return self.model.opt.timestep
-
-    def get_state(self, sig=None):
-      if sig is not None:
-        raise NotImplementedError('state signatures are served by the facade')
-      parts = [self.data.qpos, self.data.qvel] + ([self.data.act] if self.model.na else [])
-      return np.concatenate(parts, axis=-1)
-
-    def step(self, *a, **k): raise TypeError('the symbolic view does not step')
-    forward = reset = after_reset = set_control = step
-
-    def free(self):
-      pass
-
-    def __del__(self):
-      pass
-  SymView.__name__ = 'Sym' + cls.__name__
-  return SymView
+  """`cls` (a suite domain's Physics) at batch size 1 whose `data` arrays are SArr leaves.  (What the task hung on the
+  physics is set on the instance by TaskProgram: nothing of it reaches the view's `__getattr__`.)"""
+  return task_arrays.make_view_class(cls, 'Sym', leaf=_leaves, built_by='FusedDeviceEnv', read_only='the symbolic view is read-only',
+                                     no_step='the symbolic view does not step')
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -776,40 +666,6 @@ def _compile(src, verbose=False, extra_key=''):
 
 
 _STATE_FIELDS = ('qpos', 'qvel', 'act', 'qacc_warmstart', 'time')
-_NOT_ATTRS = ('model', 'batch', 'data', 'named', 'batch_size', 'legacy_step')
-
-
-def episode_attrs(p, B):
-  """What the task hung on the physics at episode start (targets, radii ...): name -> ((B, w) float array, the shape one
-  environment's code sees).  Float arrays with a leading batch axis (any float array when B == 1, where the ports drop
-  that axis)."""
-  out = collections.OrderedDict()
-  for k, val in vars(p).items():
-    if k.startswith('_') or k in _NOT_ATTRS:
-      continue
-    if isinstance(val, np.ndarray) and val.dtype.kind == 'f' and val.ndim >= 1 and (val.shape[0] == B or B == 1):
-      batched = val.shape[0] == B and B > 1
-      v = val.reshape(B, -1) if batched else val.reshape(1, -1)
-      out[k] = (np.ascontiguousarray(v), tuple(val.shape[1:]) if batched else tuple(val.shape))
-  return out
-
-
-def field_rows(p, names):
-  rows = {}
-  for name in names:
-    try:
-      r = p.batch._rows      # pylint: disable=protected-access
-      nrow = r(name)[0] if callable(r) else (r[name] if name in r else int(np.asarray(p.batch.get(name)).shape[1]))
-    except Exception:      # pylint: disable=broad-except
-      continue
-    if nrow:
-      rows[name] = int(nrow)
-  return rows
-
-
-def served_fields():
-  from dm_control_amd import physics as facade
-  return [n for n in facade._FIELD_AXES if n not in ('xanchor', 'xaxis', 'ten_length', 'ten_velocity')] + ['time', 'ncon']      # pylint: disable=protected-access
 
 
 def trace(host_env, precision=64, title='task'):
@@ -832,29 +688,19 @@ class TaskProgram:
     _G = g
     try:
       v = object.__new__(view_cls)
-      v.__dict__.update(_host=host_physics, _rows=rows, _attrs=attrs, model=host_physics.model, batch_size=1)
-      v.__dict__['data'] = _SymData(v)
+      v.__dict__.update(_host=host_physics, _fields=rows, model=host_physics.model, batch_size=1)
       # what the task hung on the physics at episode start: INSTANCE attributes of the view (the domain classes declare
       # them as class attributes -- `target_xy = None` -- which a plain lookup finds before __getattr__): per-environment
       # arrays as expression leaves, everything else (radii, flags) as the host's value
-      for k, val in vars(host_physics).items():
-        if not k.startswith('_') and k not in _NOT_ATTRS and k not in attrs:
+      for k, val in task_arrays.task_attrs(host_physics):
+        if k not in attrs:
           v.__dict__[k] = val
       for k, (width, shape) in attrs.items():
         leaves = np.empty(width, dtype=object)
         for j in range(width):
           leaves[j] = g.attr(k, j, width)
         v.__dict__[k] = SArr(leaves.reshape(shape))
-      from dm_control_amd import physics as facade
-      named = facade._Named()      # pylint: disable=protected-access
-      named.model = host_physics.named.model
-      named.data = facade._Named()      # pylint: disable=protected-access
-      axes = facade._make_axes(host_physics.model)      # pylint: disable=protected-access
-      for field, (rowkind, ncol) in facade._FIELD_AXES.items():      # pylint: disable=protected-access
-        if field in rows:
-          cols = facade._Axis(facade._COLS[ncol]) if ncol else None      # pylint: disable=protected-access
-          setattr(named.data, field, facade.FieldIndexer(lambda f=field: getattr(v.data, f), axes[rowkind], cols, False))
-      v.__dict__['named'] = named
+      task_arrays.build_named(v, host_physics, rows, False)
       obs = task.get_observation(v)
       self.observation_layout = collections.OrderedDict()
       obs_nodes = []
@@ -941,7 +787,7 @@ def _cstruct(fields):
   return S
 
 
-class FusedDeviceEnv:
+class FusedDeviceEnv(task_arrays.TaskEnv):
   """B environments of `suite.<domain>.<task>` resident on one GPU, the task layer as one generated kernel; `step(action)`
   -> (obs (B, n), reward (B,), done (B,)) device tensors; `first`, `discount`, `terminated` hold the step's other flags.
   See the module docstring.  `pool_rounds` start states per environment are drawn by the host port's `initialize_episode`
@@ -953,34 +799,15 @@ class FusedDeviceEnv:
     generated function as its epilogue: one hipcc run of 15 - 25 s, cached) -- an environment step is then the physics
     launch alone; False, or when that build is not possible: the same function as a small kernel of its own behind the
     physics launch."""
-    import torch
-    from dm_control_amd import suite
-    self.torch = torch
-    self.B = int(batch_size)
-    self.device = torch.device('cuda', device_id)
-    self.dtype = torch.float32 if precision == 32 else torch.float64
     self.precision = precision
-    kw = dict(task_kwargs or {})
-    kw.setdefault('random', seed)
-    pk = dict(batch_size=self.B, precision=precision, device_id=device_id)
-    if inline:
-      pk['specialise'] = 'cached'      # (the kernel specialised for (model, TASK) replaces the model's plain one below: no point in building that)
-    self.host_env = suite.load(domain, task, task_kwargs=kw, physics_kwargs=pk)
-    p = self.host_env.physics
-    self.host_physics, self.task, self.model = p, self.host_env.task, p.model
-    self.n_sub_steps = int(self.host_env._n_sub_steps)      # pylint: disable=protected-access
-    lim = self.host_env._step_limit      # pylint: disable=protected-access
+    # (inline: the kernel specialised for (model, TASK) replaces the model's plain one below: no point in building that)
+    lim = self._load_host(domain, task, batch_size, precision, device_id, seed, task_kwargs, **(dict(specialise='cached') if inline else {}))
     self.step_limit = 2 ** 30 if lim == float('inf') else int(math.ceil(float(lim)))
+    torch, p = self.torch, self.host_physics
     p.batch.wait_specialised()      # (a launch recorded into a HIP graph keeps the kernel it was captured with)
-    # bind every field the facade serves from the device to a torch tensor (zero copy)
-    self._tensors = {}
-    rows = field_rows(p, served_fields() + ['env_mode'])
-    for name, nrow in rows.items():
-      dt = torch.float64 if name == 'time' else torch.int32 if name in ('ncon', 'nefc', 'solver_iter', 'env_mode') else self.dtype
-      t = torch.zeros((nrow, self.B), dtype=dt, device=self.device)
-      p.batch.bind(name, t.data_ptr())
-      self._tensors[name] = t
-    rows.pop('env_mode')
+    # every field the facade serves from the device, bound to a torch tensor (zero copy)
+    self._bind_fields(served_fields() + ['env_mode'])
+    rows = {name: t.shape[0] for name, t in self._tensors.items() if name != 'env_mode'}
     # ---- the start-state pool: the host port's own initialize_episode, `pool_rounds` times for the whole batch
     self.rounds = int(pool_rounds)
     self._state_names = [f for f in _STATE_FIELDS if f in rows]
@@ -1103,9 +930,6 @@ class FusedDeviceEnv:
       raise RuntimeError('fused_restart: hip error %d' % rc)
 
   # -- stepping ----------------------------------------------------------------------------------------------------------
-  def _stream(self):
-    return self.torch.cuda.current_stream().cuda_stream
-
   def _launches(self):
     st = self._stream()
     b = self.host_physics.batch
@@ -1133,19 +957,8 @@ class FusedDeviceEnv:
       self.ctrl.copy_(action.T)      # (B, nu) -> the batch's (nu, B) control rows
     if self._capture:
       if self._graph is None:
-        saved = [self.pending, self.steps, self.episode, self._tensors['env_mode']] + [self._tensors[f] for f in self._state_names] + list(self._attr_live.values())
-        keep = [t.clone() for t in saved]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-          self._launches()      # warm-up off the default stream, as graph capture requires
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-          self._launches()
-        for t, v in zip(saved, keep):
-          t.copy_(v)      # the warm-up run is taken back: the replay below is this call's step
-        self._graph = graph
+        carried = [self.pending, self.steps, self.episode, self._tensors['env_mode']] + [self._tensors[f] for f in self._state_names] + list(self._attr_live.values())
+        self._graph, _ = task_arrays.capture_step(torch, self._launches, carried)
       self._graph.replay()
     else:
       self._launches()
@@ -1159,13 +972,6 @@ class FusedDeviceEnv:
     self.restart()
     z = self.torch.zeros((self.B, self.model.nu), dtype=self.dtype, device=self.device)
     return self.step(z)[0]
-
-  def warnings(self):
-    return self.host_physics.batch.get('warning')
-
-  def close(self):
-    self._graph = None
-    self.host_physics.free()
 
 
 def make(domain, task, batch_size, **kwargs):

@@ -25,6 +25,7 @@ import numpy as np
 from dm_control_amd import mjcf_compiler
 from dm_control_amd.batch import BatchedPhysics, OUT
 from dm_control_amd.suite import common
+from dm_control_amd.suite.task_arrays import capture_step
 
 
 def tolerance(torch, x, bounds=(0.0, 0.0), margin=0.0, sigmoid='gaussian', value_at_margin=0.1):
@@ -201,18 +202,7 @@ class TorchBatchedEnv:
       self.physics.wait_specialised()      # (a graph keeps the kernel it was captured with)
       self._g_action = action.clone()
       state = [self.qpos, self.qvel, self.warm, self.time, self.ctrl, self.steps] + ([self.act] if self.model.na else [])
-      saved = [t.clone() for t in state]
-      side = torch.cuda.Stream()
-      side.wait_stream(torch.cuda.current_stream())
-      with torch.cuda.stream(side):              # warm-up off the default stream, as graph capture requires
-        self._steady_step(self._g_action)
-      torch.cuda.current_stream().wait_stream(side)
-      graph = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(graph):
-        self._g_out = self._steady_step(self._g_action)
-      for t, v in zip(state, saved):             # the warm-up step is taken back: the replay below is this call's step
-        t.copy_(v)
-      self._graph = graph
+      self._graph, self._g_out = capture_step(torch, lambda: self._steady_step(self._g_action), state)
     self._g_action.copy_(action)
     self._graph.replay()
     return self._g_out

@@ -303,6 +303,33 @@ def test_torch_batched_env_matches_host_env_semantics():
   env.close()
 
 
+def test_torch_env_captured_graph_equals_eager_across_a_restart():
+  """`capture=True`: the steps in which no environment can reach the time limit are replays of one HIP graph, the others
+  (the restart among them) run eagerly.  Same seed, same actions: observation, reward and done of every step equal the
+  eager environment's bit for bit (the same kernels in the same order on the same start states: the draws are keyed by
+  seed and per-environment draw count) -- over a 5-step time limit crossed twice."""
+  import torch
+  from dm_control_amd.suite import torch_env
+  B = 64
+  outs = []
+  for capture in (False, True):
+    env = torch_env.make('cheetah', 'run', B, precision=32, seed=1, time_limit=0.05, capture=capture)
+    assert env.step_limit == 5
+    g = torch.Generator(device='cuda').manual_seed(0)
+    log = []
+    for _ in range(13):
+      obs, rew, done = env.step(torch.rand((B, env.model.nu), device='cuda', generator=g) * 2 - 1)
+      log.append((obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy()))
+    outs.append(log)
+    env.close()
+  for a, b in zip(*outs):
+    for x, y in zip(a, b):
+      np.testing.assert_array_equal(x, y)
+  done = np.stack([l[2] for l in outs[1]])      # (step, env)
+  assert done[[4, 9]].all() and not done[[0, 1, 2, 3, 5, 6, 7, 8, 10, 11, 12]].any()
+  assert all(np.isfinite(l[0]).all() for l in outs[1])
+
+
 @pytest.mark.parametrize('name,nsub', [('walker', 10), ('hopper', 4), ('pendulum', 1), ('acrobot', 1),
                                        ('finger', 2), ('reacher', 1), ('point_mass', 1), ('fish', 10), ('ball_in_cup', 10),
                                        ('swimmer6', 15), ('quadruped', 4), ('stacker', 10), ('manipulator', 10)])
