@@ -20,6 +20,7 @@ EXPORTS = [
     'dmc_batch_prof_get', 'dmc_gather_create', 'dmc_gather_destroy', 'dmc_gather_run',
     'dmc_batch_set_env_geoms', 'dmc_env_geom_pack', 'dmc_batch_wave_trace', 'dmc_batch_randomize_joints',
     'dmc_batch_attach_specialised', 'dmc_batch_set_task_args', 'dmc_batch_enable_task',
+    'dmc_camera_create', 'dmc_camera_destroy', 'dmc_camera_set_colors', 'dmc_camera_set_tuning', 'dmc_camera_render',
 ]
 
 _lib = None
@@ -100,6 +101,13 @@ def lib():
   if hasattr(L, 'dmc_batch_set_task_args'):
     L.dmc_batch_set_task_args.argtypes = [vp, vp, ci]
     L.dmc_batch_enable_task.argtypes = [vp, ci]
+  if hasattr(L, 'dmc_camera_create'):
+    L.dmc_camera_create.argtypes = [vp, ci, vp, ci, ci, vp, ctypes.POINTER(vp)]
+    L.dmc_camera_destroy.argtypes = [vp]
+    L.dmc_camera_destroy.restype = None
+    L.dmc_camera_set_colors.argtypes = [vp, vp, vp]
+    L.dmc_camera_set_tuning.argtypes = [vp, ci, ci]
+    L.dmc_camera_render.argtypes = [vp, ci, vp, vp, vp, vp]
   _lib = L
   return L
 

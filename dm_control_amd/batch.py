@@ -42,6 +42,7 @@ class BatchedPhysics:
       self._model_ptr = None
       _native.check(rc)
     self.legacy_step = True
+    self.output_mask = OUT_ALL      # what set_output_mask last asked for (the library's default: every derived array)
     # a model without a baked specialised kernel takes the one built for it on demand, if there is one (specialise.py)
     self._user_caps = (int(nconmax), int(njmax), int(njcon))
     from dm_control_amd import specialise as _spec
@@ -205,6 +206,7 @@ class BatchedPhysics:
 
   def set_output_mask(self, mask):
     _native.check(_native.lib().dmc_batch_set_output_mask(self._ptr, int(mask)))
+    self.output_mask = int(mask)
 
   def set_opt(self, name, value):
     L = _native.lib()

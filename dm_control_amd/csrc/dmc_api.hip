@@ -58,6 +58,7 @@ struct dmc_batch {
   std::vector<Field> fields;
   std::map<std::string, int> index;
   int outmask;
+  int launched_mask = 0;      // the output mask the last step / forward launch ran with (what the derived arrays in HBM hold)
   int ndebug;
   void* d_debug;
   int* d_debug_i;
@@ -468,6 +469,7 @@ static int launch(dmc_batch* b, int nstep, int legacy, int mode, void* stream, c
 }
 static int launch_untimed(dmc_batch* b, int nstep, int legacy, int mode, void* stream, const SeqArgs* sq) {
   HIP_TRY(hipSetDevice(b->device));
+  b->launched_mask = b->outmask;      // what the derived arrays in HBM hold from now on (dmc_camera_render checks it)
   if (b->tb.opts.eg_n) b->tb.opts.eg_data = find_field(b, "env_geom")->dev;      // follows dmc_batch_bind
   b->tb.opts.xfrc = b->xfrc_on ? find_field(b, "xfrc_applied")->dev : nullptr; b->tb.opts.xfrc_B = b->B;
   if (b->tb.L.d.nmocap) { b->tb.opts.mocap_pos = find_field(b, "mocap_pos")->dev; b->tb.opts.mocap_quat = find_field(b, "mocap_quat")->dev; b->tb.opts.mocap_B = b->B; }      // follow dmc_batch_bind
@@ -1410,4 +1412,152 @@ extern "C" int dmc_batch_prof_get(dmc_batch* b, double* dst, int* n) {
   for (int k = 0; k < 32; k++) { double s = 0; for (int e = 0; e < b->B; e++) s += (double)tmp[(size_t)k * b->B + e]; dst[k] = s / b->B; }
   *n = 32;
   return 0;
+}
+
+// ---- batched ray-cast cameras (camera_core.h, camera_kernels.hip) ----------------------------------------------
+#include "camera_core.h"
+struct dmc_camera {
+  dmc_batch* b;
+  int ncam, H, W, ngeom, nmat, need_mask, cull, pretransform;
+  double near_, far_, ambient, diffuse, bg[3];
+  std::vector<int> matid;
+  void* d_cams; int* d_type; int* d_skip; float* d_color;
+  int f_gpos, f_gmat, f_xpos, f_xmat, f_com;      // field indices
+};
+template <typename T>
+static void cam_spec_to_dev(const dmc_camera_spec& s, int H, CamDev<T>* d) {
+  d->mode = s.mode; d->body = s.bodyid; d->target = s.targetbodyid; d->pad = 0;
+  for (int k = 0; k < 3; k++) { d->pos[k] = (T)s.pos[k]; d->pos0[k] = (T)s.pos0[k]; d->poscom0[k] = (T)s.poscom0[k]; }
+  for (int k = 0; k < 9; k++) { d->mat[k] = (T)s.mat[k]; d->mat0[k] = (T)s.mat0[k]; }
+  d->inv_f = (T)(tan(0.5*s.fovy*3.14159265358979323846/180.0)/(0.5*H));
+}
+extern "C" int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* specs, int height, int width,
+                                 const dmc_camera_options* opt, dmc_camera** out) {
+  if (!b || !specs || !out || !opt) return fail("null argument");
+  if (ncam < 1 || height < 1 || width < 1) return fail("camera count and image size must be positive");
+  const HostModel& m = b->model->hm;
+  int need = OUT_GEOM;
+  for (int i = 0; i < ncam; i++) {
+    const dmc_camera_spec& s = specs[i];
+    if (s.mode < CAM_FIXED || s.mode > CAM_TARGETBODYCOM) return fail("camera mode out of range");
+    if (s.bodyid < 0 || s.bodyid >= m.nbody) return fail("camera body out of range");
+    if (s.mode >= CAM_TARGETBODY && (s.targetbodyid < 0 || s.targetbodyid >= m.nbody)) return fail("a targetbody camera needs a target body");
+    if (!(s.fovy > 0 && s.fovy < 180)) return fail("camera fovy must lie in (0, 180) degrees");
+    if (s.mode == CAM_TRACK) need |= OUT_XPOS;
+    else if (s.mode == CAM_TRACKCOM) need |= OUT_SUBTREE_COM;
+    else need |= OUT_XPOS | OUT_XMAT | (s.mode == CAM_TARGETBODYCOM ? OUT_SUBTREE_COM : 0);
+  }
+  if (!(opt->near_m >= 0) || !(opt->far_m > opt->near_m)) return fail("camera clip range: need 0 <= near < far");
+  dmc_camera* c = new dmc_camera();
+  c->b = b; c->ncam = ncam; c->H = height; c->W = width; c->ngeom = m.ngeom; c->nmat = opt->nmat; c->need_mask = need;
+  c->cull = 1; c->pretransform = 1;
+  c->near_ = opt->near_m; c->far_ = opt->far_m; c->ambient = opt->ambient; c->diffuse = opt->diffuse;
+  for (int k = 0; k < 3; k++) c->bg[k] = opt->background[k];
+  c->matid.assign(m.ngeom, -1);
+  std::vector<int> type(std::max(1, m.ngeom)), skip(std::max(1, m.ngeom));
+  for (int g = 0; g < m.ngeom; g++) {
+    type[g] = m.geom_type[g];
+    const int grp = opt->geom_group ? opt->geom_group[g] : 0;
+    const bool drawn = type[g] == DMC_GEOM_PLANE || type[g] == DMC_GEOM_SPHERE || type[g] == DMC_GEOM_CAPSULE ||
+                       type[g] == DMC_GEOM_ELLIPSOID || type[g] == DMC_GEOM_CYLINDER || type[g] == DMC_GEOM_BOX;
+    skip[g] = !drawn || m.geom_invisible[g] || grp < 0 || grp > 30 || !((opt->group_mask >> grp) & 1);
+    if (opt->geom_matid && opt->geom_matid[g] >= 0) {
+      if (opt->geom_matid[g] >= opt->nmat) { delete c; return fail("geom_matid out of range"); }
+      c->matid[g] = opt->geom_matid[g];
+    }
+  }
+  c->f_gpos = b->index["geom_xpos"]; c->f_gmat = b->index["geom_xmat"]; c->f_xpos = b->index["xpos"];
+  c->f_xmat = b->index["xmat"]; c->f_com = b->index["subtree_com"];
+  c->d_cams = nullptr; c->d_type = nullptr; c->d_skip = nullptr; c->d_color = nullptr;
+  hipError_t e = hipSetDevice(b->device);
+  const size_t ni = sizeof(int)*type.size();
+  if (e == hipSuccess) e = hipMalloc((void**)&c->d_type, ni);
+  if (e == hipSuccess) e = hipMalloc((void**)&c->d_skip, ni);
+  if (e == hipSuccess) e = hipMalloc((void**)&c->d_color, sizeof(float)*3*type.size());
+  if (e == hipSuccess) e = hipMemset(c->d_color, 0, sizeof(float)*3*type.size());
+  if (e == hipSuccess) e = hipMemcpy(c->d_type, type.data(), ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(c->d_skip, skip.data(), ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (b->precision == 64) {
+      std::vector<CamDev<double>> d(ncam);
+      for (int i = 0; i < ncam; i++) cam_spec_to_dev(specs[i], height, &d[i]);
+      e = hipMalloc(&c->d_cams, sizeof(d[0])*ncam);
+      if (e == hipSuccess) e = hipMemcpy(c->d_cams, d.data(), sizeof(d[0])*ncam, hipMemcpyHostToDevice);
+    } else {
+      std::vector<CamDev<float>> d(ncam);
+      for (int i = 0; i < ncam; i++) cam_spec_to_dev(specs[i], height, &d[i]);
+      e = hipMalloc(&c->d_cams, sizeof(d[0])*ncam);
+      if (e == hipSuccess) e = hipMemcpy(c->d_cams, d.data(), sizeof(d[0])*ncam, hipMemcpyHostToDevice);
+    }
+  }
+  if (e != hipSuccess) { dmc_camera_destroy(c); return fail(std::string("camera create: ") + hipGetErrorString(e), -2); }
+  *out = c;
+  return 0;
+}
+extern "C" void dmc_camera_destroy(dmc_camera* c) {
+  if (!c) return;
+  if (c->d_cams) (void)hipFree(c->d_cams);
+  if (c->d_type) (void)hipFree(c->d_type);
+  if (c->d_skip) (void)hipFree(c->d_skip);
+  if (c->d_color) (void)hipFree(c->d_color);
+  delete c;
+}
+extern "C" int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, const double* mat_rgba) {
+  if (!c || !geom_rgba) return fail("null argument");
+  std::vector<float> col(3*(size_t)std::max(1, c->ngeom));
+  for (int g = 0; g < c->ngeom; g++) {
+    const double* s = geom_rgba + 4*g;
+    // mjv's setMaterial: a material's colour takes over only where the geom's own rgba is the default grey
+    if (c->matid[g] >= 0 && mat_rgba && s[0] == 0.5 && s[1] == 0.5 && s[2] == 0.5 && s[3] == 1.0) s = mat_rgba + 4*c->matid[g];
+    for (int k = 0; k < 3; k++) col[3*g + k] = (float)s[k];
+  }
+  HIP_TRY(hipSetDevice(c->b->device));
+  HIP_TRY(hipMemcpy(c->d_color, col.data(), sizeof(float)*col.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+extern "C" int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform) {
+  if (!c) return fail("null camera");
+  c->cull = cull ? 1 : 0;
+  c->pretransform = pretransform ? 1 : 0;
+  return 0;
+}
+static int launch_cam(const CamArgs<float>& a, void* s) { return launch_camera_f32(a, s); }
+static int launch_cam(const CamArgs<double>& a, void* s) { return launch_camera_f64(a, s); }
+template <typename T>
+static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void* seg, void* stream) {
+  dmc_batch* b = c->b;
+  CamArgs<T> a;
+  a.geom_xpos = (const T*)b->fields[c->f_gpos].dev; a.geom_xmat = (const T*)b->fields[c->f_gmat].dev;
+  a.xpos = (const T*)b->fields[c->f_xpos].dev; a.xmat = (const T*)b->fields[c->f_xmat].dev;
+  a.subtree_com = (const T*)b->fields[c->f_com].dev;
+  a.geom_size = (const T*)b->d_mr + b->tb.L.mr_geom_size;
+  Field* eg = b->tb.opts.eg_n ? find_field(b, "env_geom") : nullptr;
+  a.eg_data = eg ? (const T*)eg->dev : nullptr; a.eg_slot = eg ? b->d_eg_slot : nullptr;
+  a.geom_type = c->d_type; a.geom_skip = c->d_skip; a.geom_color = c->d_color;
+  a.cams = (const CamDev<T>*)c->d_cams;
+  a.B = b->B; a.ngeom = c->ngeom; a.ncam = c->ncam; a.H = c->H; a.W = c->W; a.cull = c->cull; a.pretransform = c->pretransform;
+  a.near_ = (T)c->near_; a.far_ = (T)c->far_; a.ambient = (T)c->ambient; a.diffuse = (T)c->diffuse;
+  for (int k = 0; k < 3; k++) {
+    const double v = std::min(1.0, std::max(0.0, c->bg[k]));
+    a.bg[k] = (uint8_t)(int)floor(255*v + 0.5);
+  }
+  a.bg[3] = 0;
+  a.rgb = (what & CAM_RGB) ? (uint8_t*)rgb : nullptr; a.depth = (what & CAM_DEPTH) ? (T*)depth : nullptr;
+  a.seg = (what & CAM_SEG) ? (int*)seg : nullptr;
+  const int rc = launch_cam(a, stream);
+  if (rc) return fail(rc == -1 ? "camera render: the launch grid does not fit" : "camera render: launch failed", -2);
+  return 0;
+}
+extern "C" int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_dev, void* seg_dev, void* hip_stream) {
+  if (!c) return fail("null camera");
+  if (!(what_mask & (CAM_RGB | CAM_DEPTH | CAM_SEG))) return fail("camera render: nothing asked for");
+  if (((what_mask & CAM_RGB) && !rgb_dev) || ((what_mask & CAM_DEPTH) && !depth_dev) || ((what_mask & CAM_SEG) && !seg_dev))
+    return fail("camera render: null output array");
+  dmc_batch* b = c->b;
+  if ((b->outmask & b->launched_mask & c->need_mask) != c->need_mask)
+    return fail("camera render: the batch's output mask excludes arrays the cameras read (geom / xpos / xmat / subtree_com), or "
+                "did when the last step / forward launch ran (or none has run yet): the poses in device memory would be stale", -3);
+  HIP_TRY(hipSetDevice(b->device));
+  return b->precision == 64 ? camera_render_t<double>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream)
+                            : camera_render_t<float>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream);
 }

@@ -296,6 +296,56 @@ class _Opt:
     self.enableflags = 0
 
 
+def world_frames_at_qpos0(c):
+  """xpos / xquat / subtree_com at qpos0 (hinge and slide displacements zero, ball quaternions as stored): what the
+  `*0` camera / light constants of mjModel are measured in."""
+  nb = c.nbody
+  xpos, xquat = np.zeros((nb, 3)), np.tile([1.0, 0, 0, 0], (nb, 1))
+  for b in range(1, nb):
+    p, ja, jn = int(c.body_parentid[b]), int(c.body_jntadr[b]), int(c.body_jntnum[b])
+    if jn == 1 and c.jnt_type[ja] == 0:
+      a = int(c.jnt_qposadr[ja])
+      xpos[b] = c.qpos0[a:a + 3]
+      xquat[b] = c.qpos0[a + 3:a + 7] / np.linalg.norm(c.qpos0[a + 3:a + 7])
+    else:
+      xpos[b] = xpos[p] + rot_vec(xquat[p], c.body_pos[b])
+      xquat[b] = quat_mul(xquat[p], c.body_quat[b])
+      for j in range(ja, ja + jn):
+        if c.jnt_type[j] == 1:
+          a = int(c.jnt_qposadr[j])
+          xquat[b] = quat_mul(xquat[b], c.qpos0[a:a + 4] / np.linalg.norm(c.qpos0[a:a + 4]))
+  xipos = np.array([xpos[b] + rot_vec(xquat[b], c.body_ipos[b]) for b in range(nb)]).reshape(nb, 3)
+  com = xipos * np.asarray(c.body_mass, dtype=np.float64)[:, None]
+  mass = np.asarray(c.body_mass, dtype=np.float64).copy()
+  for b in range(nb - 1, 0, -1):
+    com[c.body_parentid[b]] += com[b]
+    mass[c.body_parentid[b]] += mass[b]
+  com = np.where(mass[:, None] > 0, com / np.maximum(mass[:, None], MINVAL), xipos)
+  return xpos, xquat, com
+
+
+def frame_constants(c, bodyid, pos, quat=None, frames=None):
+  """(pos0, poscom0, mat0) of elements attached to bodies `bodyid` at local `pos` / `quat`: their global offset from the
+  body origin, from the body's subtree COM, and their global orientation (n, 9), all at qpos0 -- mjModel's cam_pos0 /
+  cam_poscom0 / cam_mat0 (and light_pos0 / light_poscom0)."""
+  xpos0, xquat0, com0 = frames if frames is not None else world_frames_at_qpos0(c)
+  bodyid = np.asarray(bodyid, dtype=np.int64).reshape(-1)
+  n = bodyid.size
+  pos = np.asarray(pos, dtype=np.float64).reshape(n, 3)
+  gp = np.array([xpos0[bodyid[i]] + rot_vec(xquat0[bodyid[i]], pos[i]) for i in range(n)]).reshape(n, 3)
+  mat0 = None
+  if quat is not None:
+    quat = np.asarray(quat, dtype=np.float64).reshape(n, 4)
+    mat0 = np.array([quat_to_mat(quat_mul(xquat0[bodyid[i]], quat[i])).ravel() for i in range(n)]).reshape(n, 9)
+  return gp - xpos0[bodyid].reshape(n, 3), gp - com0[bodyid].reshape(n, 3), mat0
+
+
+def camera_constants(c):
+  """(cam_pos0, cam_poscom0, cam_mat0) of a compiled model, derived from its CURRENT arrays on every call (a model
+  whose qpos0 / body_pos / cam_pos were edited after compilation gets the constants of the edited model)."""
+  return frame_constants(c, c.cam_bodyid, c.cam_pos, c.cam_quat)
+
+
 class Model:
   """Compiled constant tables; attribute names follow mjModel."""
 
@@ -338,6 +388,11 @@ class Model:
       self.opt.disableflags = old
 
   # --- reference API: MjModel.name2id / id2name (wrapper/core.py:347-387) ---
+  # mjModel's camera constants at qpos0 (camera_constants)
+  cam_pos0 = property(lambda self: camera_constants(self)[0])
+  cam_poscom0 = property(lambda self: camera_constants(self)[1])
+  cam_mat0 = property(lambda self: camera_constants(self)[2])
+
   def name2id(self, name, object_type):
     lst = self.names.get(object_type)
     if lst is None or name not in lst:
@@ -675,7 +730,7 @@ class _Compiler:
         self.lights.append(dict(name=a.get('name'), body=bid, pos=_vec(a['pos'], 3) if 'pos' in a else np.zeros(3),
                                 dir=_vec(a['dir'], 3) if 'dir' in a else np.array([0.0, 0, -1])))
       elif tag == 'camera':
-        # rendering only (MjModel.ncam, cam_* arrays): nothing on the device reads them
+        # rendering only (MjModel.ncam, cam_* arrays): the step kernels never read them; camera.BatchCamera does
         cname = child.attrib.get('class', childclass) or 'main'
         if cname not in self.classes:
           raise MjcfError('unknown default class %r' % cname)
@@ -683,7 +738,7 @@ class _Compiler:
         a.update(child.attrib)
         self.cameras.append(a.get('name'))
         self.camera_specs.append(dict(body=bid, pos=_vec(a['pos'], 3) if 'pos' in a else np.zeros(3),
-                                      quat=self._orientation(a), fovy=float(a.get('fovy', 45)),
+                                      quat=self._orientation(a), fovy=float(a.get('fovy', 45)), target=a.get('target'),
                                       mode=('fixed', 'track', 'trackcom', 'targetbody', 'targetbodycom').index(a.get('mode', 'fixed'))))
       elif tag == 'body':
         pass  # handled below so that this body's elements get ids first
@@ -805,6 +860,7 @@ class _Compiler:
         margin=float(a.get('margin', 0)), gap=float(a.get('gap', 0)),
         mass=mass, inertia=inertia)
     g['rgba'] = _rgba(a)
+    g['material'] = a.get('material')
     if a.get('material') in getattr(self, 'material_alpha', {}):
       g['invisible'] = int(self.material_alpha[a['material']] == 0)
     else:
@@ -1127,6 +1183,15 @@ class _Compiler:
     m.cam_pos = np.array([c['pos'] for c in cs], dtype=np.float64).reshape(len(cs), 3)
     m.cam_quat = np.array([c['quat'] for c in cs], dtype=np.float64).reshape(len(cs), 4)
     m.cam_fovy = np.array([c['fovy'] for c in cs], dtype=np.float64)
+    body_names = [b['name'] for b in self.bodies]
+    for c in cs:
+      if c['mode'] >= 3 and c['target'] not in body_names:
+        raise MjcfError('camera mode targetbody / targetbodycom needs target= naming a body, got %r' % (c['target'],))
+    m.cam_targetbodyid = np.array([body_names.index(c['target']) if c['target'] in body_names else -1 for c in cs], dtype=np.int64)
+    # what the ray-cast cameras (camera.py) read beside the poses: visibility group and material of every geom
+    m.geom_group = np.array([g['group'] for g in self.geoms], dtype=np.int64)
+    mat_names = [n for n, _ in self.materials]
+    m.geom_matid = np.array([mat_names.index(g['material']) if g.get('material') in mat_names else -1 for g in self.geoms], dtype=np.int64)
     assets = [e for sec in self.root.findall('asset') for e in sec]
     custom = [e for sec in self.root.findall('custom') for e in sec]
 

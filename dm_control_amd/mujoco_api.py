@@ -332,32 +332,7 @@ _COUNT_FIELD = {'body': 'nbody', 'joint': 'njnt', 'geom': 'ngeom', 'site': 'nsit
                 'sensor': 'nsensor', 'numeric': 'nnumeric', 'text': 'ntext', 'tuple': 'ntuple', 'key': 'nkey'}
 
 
-def _world_frames_at_qpos0(c):
-  """xpos / xquat / subtree_com at qpos0 (hinge and slide displacements zero, ball quaternions as stored): what the
-  `*0` camera / light constants of mjModel are measured in."""
-  nb = c.nbody
-  xpos, xquat = np.zeros((nb, 3)), np.tile([1.0, 0, 0, 0], (nb, 1))
-  for b in range(1, nb):
-    p, ja, jn = int(c.body_parentid[b]), int(c.body_jntadr[b]), int(c.body_jntnum[b])
-    if jn == 1 and c.jnt_type[ja] == 0:
-      a = int(c.jnt_qposadr[ja])
-      xpos[b] = c.qpos0[a:a + 3]
-      xquat[b] = c.qpos0[a + 3:a + 7] / np.linalg.norm(c.qpos0[a + 3:a + 7])
-    else:
-      xpos[b] = xpos[p] + mjcf_compiler.rot_vec(xquat[p], c.body_pos[b])
-      xquat[b] = mjcf_compiler.quat_mul(xquat[p], c.body_quat[b])
-      for j in range(ja, ja + jn):
-        if c.jnt_type[j] == 1:
-          a = int(c.jnt_qposadr[j])
-          xquat[b] = mjcf_compiler.quat_mul(xquat[b], c.qpos0[a:a + 4] / np.linalg.norm(c.qpos0[a:a + 4]))
-  xipos = np.array([xpos[b] + mjcf_compiler.rot_vec(xquat[b], c.body_ipos[b]) for b in range(nb)]).reshape(nb, 3)
-  com = xipos * np.asarray(c.body_mass, dtype=np.float64)[:, None]
-  mass = np.asarray(c.body_mass, dtype=np.float64).copy()
-  for b in range(nb - 1, 0, -1):
-    com[c.body_parentid[b]] += com[b]
-    mass[c.body_parentid[b]] += mass[b]
-  com = np.where(mass[:, None] > 0, com / np.maximum(mass[:, None], mjMINVAL), xipos)
-  return xpos, xquat, com
+_world_frames_at_qpos0 = mjcf_compiler.world_frames_at_qpos0
 
 
 def _build_extras(c):
@@ -409,14 +384,12 @@ def _build_extras(c):
         break
       a = int(c.body_parentid[a])
   x['subtree'] = sub
-  xpos0, xquat0, com0 = _world_frames_at_qpos0(c)
-  for pre, n, bodyid, pos in (('cam', c.ncam, getattr(c, 'cam_bodyid', np.zeros(0, int)), getattr(c, 'cam_pos', np.zeros((0, 3)))),
-                              ('light', c.nlight, c.light_bodyid, c.light_pos)):
-    gp = np.array([xpos0[bodyid[i]] + mjcf_compiler.rot_vec(xquat0[bodyid[i]], pos[i]) for i in range(n)]).reshape(n, 3)
-    x[pre + '_pos0'] = gp - xpos0[bodyid].reshape(n, 3)
-    x[pre + '_poscom0'] = gp - com0[bodyid].reshape(n, 3)
-  x['cam_mat0'] = np.array([mjcf_compiler.quat_to_mat(mjcf_compiler.quat_mul(xquat0[c.cam_bodyid[i]], c.cam_quat[i])).ravel()
-                            for i in range(c.ncam)]).reshape(c.ncam, 9)
+  frames = xpos0, xquat0, com0 = _world_frames_at_qpos0(c)
+  # (one derivation for the facade and the ray-cast cameras: mjcf_compiler.frame_constants)
+  x['cam_pos0'], x['cam_poscom0'], x['cam_mat0'] = mjcf_compiler.frame_constants(
+      c, getattr(c, 'cam_bodyid', np.zeros(0, int)), getattr(c, 'cam_pos', np.zeros((0, 3))),
+      getattr(c, 'cam_quat', np.zeros((0, 4))), frames)
+  x['light_pos0'], x['light_poscom0'], _ = mjcf_compiler.frame_constants(c, c.light_bodyid, c.light_pos, None, frames)
   x['light_dir0'] = np.array([mjcf_compiler.rot_vec(xquat0[c.light_bodyid[i]], c.light_dir[i]) for i in range(c.nlight)]).reshape(c.nlight, 3)
   x['mesh_normal'] = np.zeros((0, 3))
   x['skin_rgba'] = np.zeros((0, 4))

@@ -488,6 +488,11 @@ class GenericDeviceEnv(task_arrays.TaskEnv):
     self._graph.replay()
     return self._g_out
 
+  def invalidate_graph(self):
+    """Drops the recorded HIP graph of the control step; the next step records it again (after a change of what the
+    launches do, e.g. the batch's output mask: suite/pixels.py)."""
+    self._graph = None
+
   def step(self, action):
     """action: (B, nu) tensor on the device.  Returns (obs, reward, done); when the time limit is reached every
     environment restarts and the returned observation is the new episode's first.  With `capture=True,

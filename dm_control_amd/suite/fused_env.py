@@ -946,6 +946,11 @@ class FusedDeviceEnv(task_arrays.TaskEnv):
     if rc:
       raise RuntimeError('fused_post: hip error %d' % rc)
 
+  def invalidate_graph(self):
+    """Drops the recorded HIP graph of the control step; the next step records it again (after a change of what the
+    launches do, e.g. the batch's output mask: suite/pixels.py)."""
+    self._graph = None
+
   def step(self, action=None):
     """action: (B, nu) device tensor -- or None when the caller has written the controls into `self.ctrl` itself (the
     batch's own (nu, B) control rows: a policy that emits that layout saves the transposing copy, the one launch a step

@@ -207,6 +207,11 @@ class TorchBatchedEnv:
     self._graph.replay()
     return self._g_out
 
+  def invalidate_graph(self):
+    """Drops the recorded HIP graph of the control step; the next step records it again (after a change of what the
+    launches do, e.g. the batch's output mask: suite/pixels.py)."""
+    self._graph = None
+
   def step(self, action):
     """action: (B, nu) tensor on device.  Returns (obs, reward, done) tensors; finished
     environments are auto-reset (their returned obs is the fresh start state).  With `capture=True, copy_outputs=False`

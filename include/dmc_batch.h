@@ -250,6 +250,50 @@ int dmc_gather_create(dmc_batch* b, int nrows, const char* const* field_names, c
 void dmc_gather_destroy(dmc_gather* g);
 int dmc_gather_run(dmc_gather* g, void* out, void* hip_stream);
 
+/* Batched ray-cast cameras.  Replace, for every environment of the batch at once and without leaving the device,
+ * Camera.render of dm_control/mujoco/engine.py:840-946 (mjv_updateScene + mjr_render + mjr_readPixels; :924 depth in
+ * metres, :930-946 segmentation as (object id, object type)) and Camera.matrix's pinhole model (engine.py:790-808).
+ * A geometric camera, not OpenGL: depth and segmentation are the nearest ray hit over the primitive geoms (plane,
+ * sphere, capsule, ellipsoid, cylinder, box; meshes and height fields are not drawn), RGB is the geom colour under a
+ * headlight at the camera -- colour * (ambient + diffuse * max(0, n . -d)) -- over a constant background; no
+ * textures, lights, shadows, sites or tendons.
+ * A spec holds one camera in mjModel's terms.  mode: 0 fixed, 1 track, 2 trackcom, 3 targetbody, 4 targetbodycom.
+ * pos / mat: cam_pos and the rotation matrix of cam_quat (row-major) in the frame of body `bodyid`; pos0 / poscom0 /
+ * mat0: mjModel's cam_pos0 / cam_poscom0 / cam_mat0 (the tracking modes); fovy in degrees. */
+typedef struct dmc_camera dmc_camera;
+typedef struct dmc_camera_spec {
+  int32_t mode, bodyid, targetbodyid, reserved;
+  double pos[3], mat[9], pos0[3], poscom0[3], mat0[9], fovy;
+} dmc_camera_spec;
+/* near_m / far_m: clip range in metres along the optical axis (hits outside it are skipped; a miss reports far_m);
+ * group_mask: bit g set = geoms of group g are drawn (mjvOption.geomgroup); geom_group / geom_matid: (ngeom) ints or
+ * NULL (all group 0 / no materials); nmat: rows of the mat_rgba later given to the colour upload. */
+typedef struct dmc_camera_options {
+  double near_m, far_m, ambient, diffuse, background[3];
+  int32_t group_mask, nmat;
+  const int32_t* geom_group;
+  const int32_t* geom_matid;
+} dmc_camera_options;
+/* Replaces engine.Camera(physics, height, width, camera_id) (engine.py:700-760) for `ncam` cameras of one image size. */
+int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* specs, int height, int width,
+                      const dmc_camera_options* options, dmc_camera** out);
+void dmc_camera_destroy(dmc_camera* c);
+/* The colours mjv_updateScene reads from mjModel at render time (engine.py:840-870; tasks recolour geoms between
+ * episodes): geom_rgba (ngeom, 4) and mat_rgba (nmat, 4) or NULL.  A material's colour replaces a geom's own only
+ * where that is MuJoCo's default (0.5, 0.5, 0.5, 1).  Synchronous. */
+int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, const double* mat_rgba);
+/* Tuning study switches, both on by default.  cull: geoms whose bounding sphere misses a pixel tile are dropped before
+ * staging.  pretransform: the staged geoms hold the ray origin and the camera rotation in the geom's frame (off: the
+ * world frame, transformed per pixel). */
+int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform);
+/* Replaces Camera.render (engine.py:840-946).  what_mask: 1 rgb, 2 depth, 4 segmentation, any subset in one launch.
+ * Outputs are caller-owned device arrays, env-major: rgb uint8 (B, ncam, H, W, 3); depth (B, ncam, H, W) in the batch
+ * precision; segmentation int32 (B, ncam, H, W, 2) = (geom id, 5 = mjOBJ_GEOM), background (-1, -1).  Draws the poses
+ * the last step / forward launch wrote (geom_xpos, geom_xmat, xpos, xmat, subtree_com) with the geom sizes the step
+ * kernel uses.  Asynchronous on `hip_stream`, never waits.  Returns -3 when the batch's output mask excludes an array
+ * the cameras read, did so when the last step / forward launch ran, or no such launch has run yet. */
+int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_dev, void* seg_dev, void* hip_stream);
+
 /* info[0..19] = {B, precision, lanes_per_env, waves_per_block, envs_per_block,
  * lds_bytes_per_block, grid, nconmax, njmax, env_scratch_bytes, static_id,
  * jac_kmax, table_lds_bytes, envs_per_cu, njdense, njcon, stash_on, stash_bytes_per_env,
