@@ -4227,19 +4227,20 @@ struct StepCore {
     // CG (mj_solPrimal with flg_Newton = 0): the gradient preconditioned with M^-1 -- the factor mj_factorM left
     // (no Hessian is ever assembled, so it is still in place)
     if (L.d.cg) { DMC_WSYNC(); chol_solve(S(sv_Mgrad), M_factor(), S(sv_grad), nv, true); DMC_PROF(PROF_SOLVE); return; }
-    if (!refactor) { DMC_WSYNC(); chol_solve(S(sv_Mgrad), S(qLH), S(sv_grad), nv, hsplit); DMC_PROF(PROF_SOLVE); return; }
 #ifndef DMC_HOST_EMU
+    // (ONE substitution call site: `refactor` is per environment, and a wave whose two environments disagree on it used to
+    // run the out-of-line substitution twice, once per side of the early return below)
     if constexpr (LS::kNV > 0 && LS::kNV <= 16 && LS::kNV <= LPE) {
       if (L.d.jfull && !L.d.msparse && !L.d.elliptic) {
         DMC_WSYNC();
-        hess_factor_rows<LS::kNV>(nefc);
-        DMC_PROF(PROF_FACTOR);
+        if (refactor) { hess_factor_rows<LS::kNV>(nefc); DMC_PROF(PROF_FACTOR); }
         chol_solve(S(sv_Mgrad), S(qLH), S(sv_grad), nv);
         DMC_PROF(PROF_SOLVE);
         return;
       }
     }
 #endif
+    if (!refactor) { DMC_WSYNC(); chol_solve(S(sv_Mgrad), S(qLH), S(sv_grad), nv, hsplit); DMC_PROF(PROF_SOLVE); return; }
 #ifdef DMC_HOST_EMU
     // The emulation factors H in full either way.  With hsplit set it checks what the device relies on: the full
     // assembly has an exact zero wherever an entry joins two trees, and the in-tree assembly produces the same bits.
@@ -4468,21 +4469,28 @@ struct StepCore {
     if (flag) { pnext->alpha = p->alpha - p->d0/p->d1; ls_eval(pnext, qg, nefc, evals, rw); }
     return flag;
   }
-  DMC_DEV T primal_search(int nefc, T gauss, T scale, T* lscost) {
+  // REGS (primal_solve_regs): M v and J v are the caller's, in registers -- `pre` brings the lane's terms of the four dof
+  // sums and its row's (jar, jv, D); everything from the reductions on is this routine's, unchanged.
+  struct LSPre { T a1, a2, a3, a4, jar, jv, D; };
+  template <bool REGS = false>
+  DMC_DEV T primal_search(int nefc, T gauss, T scale, T* lscost, const LSPre& pre = LSPre()) {
     *lscost = 0;      // cost of the returned point (relative to alpha = 0 in fp32: minus the iteration's improvement)
 #ifdef DMC_HOST_EMU
     emu_ls_counts()[0]++;
 #endif
     const int nv = L.d.nv;
+    if constexpr (!REGS) {
     mul_M(S(sv_Mv), S(sv_search));
     { const RowMap rm = row_map(); for (int i = lane; i < nefc; i += LPE) S(efc_jv)[i] = row_dot(i, S(sv_search), rm); }
     DMC_WSYNC();
+    }
     LSRows rw;
     rw.jar = rw.jv = rw.D = 0; rw.on = false; rw.gen = false; rw.kind = LSK_NONE;
     if (general_rows() && nefc <= LPE && LPE > 1) ls_load_gen(rw, nefc);
     if (L.d.elliptic && !rw.gen) ls_prepare_ell(nefc);
     T a1 = 0, a2 = 0, a3 = 0, a4 = 0;
     const bool anch = anchored();
+    if constexpr (REGS) { a1 = pre.a1; a2 = pre.a2; a3 = pre.a3; a4 = pre.a4; } else
     FOR_LANES(i, nv) {
       const T sr = S(sv_search)[i];
       if (anch) a1 += sr*S(sv_grad)[i];      // grad . search: the slope at alpha = 0 itself (see ls_anchored)
@@ -4497,6 +4505,7 @@ struct StepCore {
     const int lsmax = o.ls_iterations;
     int evals = 0;
 #ifndef DMC_HOST_EMU
+    if constexpr (REGS) { rw.on = true; rw.jar = pre.jar; rw.jv = pre.jv; rw.D = pre.D; } else
     if (!general_rows() && nefc <= LPE) {
       rw.on = true;
       if (lane < nefc) { rw.jar = S(efc_jar)[lane]; rw.jv = S(efc_jv)[lane]; rw.D = S(efc_D)[lane]; }
@@ -5341,7 +5350,257 @@ struct StepCore {
   }
   // mj_solPrimal (Newton / CG) from S(qacc) over every dof and row of the environment; `evaluated`: M a, J a - aref, the
   // forces, the active set and the cost (cc, gauss, changed) of the starting point are already in place
+  // ---- the Newton solve of the small dense models IN REGISTERS ------------------------------------------------------
+  // Model-specialised kernels with nv <= 16, dense M, every row dense and one-sided (the family that takes
+  // hess_factor_rows), and at most kNewtonRows rows in this environment: the whole of primal_solve runs on registers.
+  // Lane i < N holds dof i -- row i of M, column i of J (J[r][i] for the rows r below the cap), qacc, qacc_smooth,
+  // qfrc_smooth, M a, M v, the gradient, the search direction, and row i AND column i of H's factor; lane r < nefc holds
+  // constraint row r -- J[r][0 .. N), D, jar, jv, its state and its force.  Both roles sit in the first 16-lane row of the
+  // group, so every cross-lane read is a DPP row broadcast (bcast_rows).  Everything is loaded once at entry and what the
+  // rest of the step reads (qacc, qfrc_constraint, efc_force, efc_jar, efc_active) is stored once at the exit: the LDS
+  // form paid a fence and a dependent LDS round trip (74-80 cycles) per phase, about twenty per iteration, and a launch
+  // lasts as long as the wave with the most iterations.
+  // The arithmetic is the LDS path's, sum for sum in the same order (dot_n / row_dot by ascending index, J'f by ascending
+  // row in trips of four with the padding rows of a trip entering as they do there, group_sum's tree over the same lanes,
+  // hess_factor_rows' elimination, chol_solve_rows' sweeps): the fp64 kernel is bit-identical to the one built with
+  // -DDMC_NO_NEWTON_REGS (tests/test_gpu_newton_regs.py).  The factor never leaves the registers: the column a lane needs
+  // for the back substitution is what the elimination broadcasts at the lane's own step (L[j][k], j > k, goes to every
+  // lane at step k; lane k keeps it), and it survives the iterations whose active set did not change.
+#if !defined(DMC_HOST_EMU) && !defined(DMC_NO_NEWTON_REGS)
+#ifndef DMC_NEWTON_REGS_F64_NV
+#define DMC_NEWTON_REGS_F64_NV 0       // fp64: the largest nv that takes the register solve.  None by default: the fp64 kernels sit at the 256-VGPR cap and every one of them gained private segment with it; tests/test_gpu_newton_regs.py builds the fp64 plugin with 16 for the bit comparison
+#endif
+  static constexpr bool kNewtonRegs = LS::kNV > 0 && LS::kNV <= 16 && LS::kNV <= LPE && LPE >= 16
+                                      && (sizeof(T) == 4 || LS::kNV <= DMC_NEWTON_REGS_F64_NV);
+#else
+  static constexpr bool kNewtonRegs = false;
+#endif
+#ifndef DMC_EPS_IMP
+#define DMC_EPS_IMP 1      // (see primal_solve)
+#endif
+  static constexpr int kNewtonRows = 16;      // rows per environment the register solve takes (one lane each, first 16-lane row)
+#ifndef DMC_HOST_EMU
+  // fp32 is compiled with contraction on, and which of the LDS path's products end up fused into their sum is decided by
+  // the vectoriser, not by the source: dot_n's products are paired off its vector loads into v_pk_mul_f32 and ADDED (no
+  // FMA), constraint_force_to_joint's trips add their first two products and fuse the other two.  The register forms of
+  // the two say so explicitly (contraction off in their bodies, the fused terms as fmaf) -- left to the compiler, nr_dot
+  // fused some of its terms and nr_jtf none, a last-bit difference per sum that a chaotic model turns into another
+  // trajectory within a few hundred steps.  Everything else is one product or one explicit FMA per sum in both paths.
+  // sum_j m[j] * (lane j's v) by ascending j: dot_n over a row of M or of J
+  template <int N> DMC_DEV T nr_dot(const T (&m)[N], T v) const {
+#pragma clang fp contract(off)
+    T s = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) { const T t = m[j] * bcast_rows<LPE, N>(v, j); s = s + t; }
+    return s;
+  }
+  // (J' force)_i: constraint_force_to_joint's dense branch
+  DMC_DEV T nr_jtf(const T (&Jc)[kNewtonRows], T force, int nefc) const {
+#pragma clang fp contract(off)
+    T f = 0;
+#pragma unroll
+    for (int r = 0; r < kNewtonRows; r += 4) if (r < nefc) {
+      T fr[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) fr[u] = bcast_rows<LPE, kNewtonRows>(force, r + u);      // (the lanes past nefc hold a zero force)
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if constexpr (sizeof(T) == 4) { if (u < 2) { const T t = Jc[r + u]*fr[u]; f = f + t; } else f = __builtin_fmaf(Jc[r + u], fr[u], f); }
+        else f = fr[u] != 0 ? f + Jc[r + u]*fr[u] : f;
+      }
+    }
+    return f;
+  }
+  // hess_factor_rows on the register copies; leaves lane i's row of the factor (zeros from the diagonal on), its column
+  // (zeros down to the diagonal) and 1 / L[i][i] -- what chol_solve_rows loads from the packed triangle
+  template <int N> DMC_DEV void nr_factor(const T (&M)[N], const T (&Jc)[kNewtonRows], T wD, int nefc, T (&row)[N], T (&col)[N], T& dinv) const {
+    const bool own = lane < N;
+    T a[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) { a[j] = M[j]; col[j] = 0; }
+#pragma unroll
+    for (int r = 0; r < kNewtonRows; r += 4) if (r < nefc) {
+      T c[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) c[u] = bcast_rows<LPE, kNewtonRows>(wD, r + u)*Jc[r + u];      // (wD: D of a row in the quadratic zone, else 0)
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+#pragma unroll
+        for (int j = 0; j < N; j++) a[j] += c[u] * bcast_rows<LPE, N>(Jc[r + u], j);
+      }
+    }
+    dinv = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+      T akk = bcast_rows<LPE, N>(a[k], k);
+      if (akk < (T)DMC_MINVAL) akk = (T)DMC_MINVAL;
+      const T inv = t_rsqrt(akk);
+      const T lik = a[k] * inv;
+#pragma unroll
+      for (int j = k + 1; j < N; j++) {
+        const T ljk = bcast_rows<LPE, N>(lik, j);
+        a[j] = nmsub<true>(a[j], lik, ljk);
+        col[j] = lane == k ? ljk : col[j];
+      }
+      row[k] = (own && k < lane) ? lik : (T)0;
+      dinv = lane == k ? inv : dinv;
+    }
+  }
+  // chol_solve_rows' two sweeps
+  template <int N> DMC_DEV T nr_solve(const T (&row)[N], const T (&col)[N], T dinv, T b) const {
+    T sreg = lane < N ? b : (T)0;
+#pragma unroll
+    for (int k = 0; k < N; k++) { const T xk = bcast_rows<LPE, N>(sreg*dinv, k); sreg = nmsub<true>(sreg, row[k], xk); }
+    sreg = sreg*dinv;
+#pragma unroll
+    for (int k = N - 1; k >= 0; k--) { const T xk = bcast_rows<LPE, N>(sreg*dinv, k); sreg = nmsub<true>(sreg, col[k], xk); }
+    return sreg*dinv;
+  }
+  // constraint_update's one-sided branch for the lane's row, with the change tracking
+  DMC_DEV T nr_update(bool rown, T jar, T D, T& force, int& act, int* changed) const {
+    T cost = 0;
+    int ch = 0;
+    if (rown) {
+      const int a = jar < 0;
+      const T dj = D*jar;
+      force = a ? -dj : (T)0;
+      if (sizeof(T) == 4) cost += a ? (T)0.5*dj*jar : (T)0; else if (a) cost += (T)0.5*D*jar*jar;
+      ch |= act != a; act = a;
+    }
+    cost = group_sum<LPE>(cost);
+    *changed = group_max<LPE>(ch);
+    return cost;
+  }
+  template <int N>
+  DMC_DEV int primal_solve_regs(int nefc, bool evaluated, T cc, T gauss, int changed) {
+    const bool own = lane < N, rown = lane < nefc;
+    const int i = own ? lane : 0, rl = rown ? lane : 0;
+    const T scale = 1 / (o.meaninertia * (T)(N > 1 ? N : 1));
+    // the one LDS round trip of the solve: unpredicated loads from in-range addresses, the values selected afterwards
+    // (fp64, a test build only: the lane's rows of M and J are read again where they are used, one round trip at the
+    // head of an iteration and one per refactorisation, instead of being kept; nothing writes them during the solve)
+    constexpr bool keep = sizeof(T) == 4;
+    T M[N], Jr[N], Jc[kNewtonRows], row[N], col[N], dinv = 0;
+    auto load_M = [&]() __attribute__((always_inline)) {
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < N; j++) M[j] = S(qM)[i*N + j];
+    };
+    auto load_Jr = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < N; j++) Jr[j] = S(efc_Jd)[rl*N + j];
+    };
+    load_M(); load_Jr();
+#pragma unroll
+    for (int r = 0; r < kNewtonRows; r++) {      // (a trip's padding rows hold the trip's first row, as hess_factor_rows / constraint_force_to_joint read them)
+      const int t = r & ~3, rr = r < nefc ? r : (t < nefc ? t : 0);
+      Jc[r] = S(efc_Jd)[rr*N + i];
+    }
+    T qacc = S(qacc)[i];
+    const T qas = S(qacc_smooth)[i], qfs = S(qfrc_smooth)[i];
+    const T D_ = S(efc_D)[rl], aref_ = S(efc_aref)[rl], Ma_ = S(sv_Ma)[i], jar_ = S(efc_jar)[rl], force_ = S(efc_force)[rl];
+    const int act_ = SI(efc_active)[rl];
+    const T D = rown ? D_ : (T)0;
+    T Ma, jar, force = 0;
+    int act;
+    auto gauss_cost_regs = [&]() __attribute__((always_inline)) {
+      T g = 0;
+      if (own) g += (Ma - qfs) * (qacc - qas);
+      return (T)0.5 * group_sum<LPE>(g);
+    };
+    if (!evaluated) {
+      Ma = nr_dot<N>(M, qacc);
+      const T ja = nr_dot<N>(Jr, qacc) - aref_;
+      jar = rown ? ja : (T)0;
+      changed = 1;
+      act = -1;      // no factor of H yet
+      cc = nr_update(rown, jar, D, force, act, &changed);
+      gauss = gauss_cost_regs();
+    } else { Ma = Ma_; jar = rown ? jar_ : (T)0; force = rown ? force_ : (T)0; act = act_; }
+    T cost = cc + gauss;
+    DMC_PROF(PROF_SOL_INIT);
+    T fc, grad, Mgrad;
+    auto gradient_regs = [&](int refactor) __attribute__((always_inline)) {
+      fc = nr_jtf(Jc, force, nefc);
+      grad = Ma - qfs - fc;
+      DMC_PROF(PROF_SOL_GRAD);
+      if (refactor) {
+        if constexpr (!keep) load_M();
+        nr_factor<N>(M, Jc, (rown && act == EFC_ST_QUADRATIC) ? D : (T)0, nefc, row, col, dinv);
+        DMC_PROF(PROF_FACTOR);
+      }
+      Mgrad = nr_solve<N>(row, col, dinv, grad);
+      DMC_PROF(PROF_SOLVE);
+    };
+    gradient_regs(1);
+    T search = -Mgrad;
+    DMC_PROF(PROF_SOL_GRAD);
+    int iter = 0;
+    const bool anch = anchored();
+    while (iter < o.iterations) {
+      if (iter == DMC_PRIO_ITER) __builtin_amdgcn_s_setprio(2);      // (see primal_solve)
+      T lscost = 0;
+      DMC_TSUB(3, iter == 0, 4);
+      // primal_search's set-up
+      if constexpr (!keep) { load_M(); load_Jr(); }
+      const T Mv = nr_dot<N>(M, search);
+      const T jv_ = nr_dot<N>(Jr, search);
+      const T jv = rown ? jv_ : (T)0;
+      T a1 = 0, a2 = 0, a3 = 0, a4 = 0;
+      if (own) {
+        const T sr = search;
+        if (anch) a1 += sr*grad;
+        else { a1 += sr*Ma; a2 += qfs*sr; }
+        a3 += sr*Mv; a4 += sr*sr;
+      }
+      LSPre pre;
+      pre.a1 = a1; pre.a2 = a2; pre.a3 = a3; pre.a4 = a4; pre.jar = jar; pre.jv = jv; pre.D = D;
+      const T alpha = primal_search<true>(nefc, gauss, scale, &lscost, pre);
+      DMC_PROF(PROF_SOL_LS);
+      DMC_TSUB(3, iter == 0, 5);
+      if (alpha == 0) break;
+      if constexpr (sizeof(T) == 4) {      // (one FMA each, as the LDS path's updates compile)
+        qacc = __builtin_fmaf(alpha, search, qacc); Ma = __builtin_fmaf(alpha, Mv, Ma);
+        jar = __builtin_fmaf(alpha, jv, jar);
+      } else { qacc += alpha*search; Ma += alpha*Mv; jar += alpha*jv; }
+      const T oldcost = cost;
+      cc = nr_update(rown, jar, D, force, act, &changed);
+      gauss = gauss_cost_regs();
+      cost = cc + gauss;
+      DMC_PROF(PROF_SOL_UPD);
+      DMC_TSUB(3, iter == 0, 6);
+      gradient_regs(changed);
+      DMC_PROF(PROF_SOL_GRAD);
+      DMC_TSUB(3, iter == 0, 7);
+      T g2 = 0, ma2 = 0;
+      search = -Mgrad;
+      if (own) { g2 += grad*grad; ma2 += Ma*Ma; }
+      g2 = group_sum<LPE>(g2); ma2 = group_sum<LPE>(ma2);
+      const T improvement = ls_relative<T>() ? -scale*lscost : scale*(oldcost - cost), gradient = scale*t_sqrt(g2);
+      iter++;
+      // primal_solve's termination tests
+      const T ulp = sizeof(T) == 4 ? (T)1.1920929e-7 : (T)2.220446049250313e-16;
+      const T tol_imp = ls_relative<T>() ? o.tolerance : t_max(o.tolerance, (T)DMC_EPS_IMP*ulp*scale*t_abs(cost));
+      const bool exact_step = sizeof(T) == 4 && !changed && t_abs(alpha - 1) < (T)1e-3;
+      const T tol_grad = t_max(o.tolerance, (exact_step ? 64 : 8)*ulp*scale*t_sqrt(ma2));
+      if (improvement < tol_imp || gradient < tol_grad) break;
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // the one exit: what the rest of the step reads
+    if (own) { S(qacc)[lane] = qacc; S(qfrc_constraint)[lane] = fc; }
+    if (rown) { S(efc_force)[lane] = force; S(efc_jar)[lane] = jar; SI(efc_active)[lane] = act; }
+    DMC_WSYNC();
+    return iter;
+  }
+#endif
   DMC_DEV int primal_solve(int nefc, bool evaluated, T cc, T gauss, int changed) {
+#ifndef DMC_HOST_EMU
+    if constexpr (kNewtonRegs) {
+      // (per environment: the two environments of a wave may take different paths)
+      if (L.d.jfull && !L.d.msparse && !L.d.elliptic && !L.d.cg && !L.d.nslip && !general_rows() && nefc <= kNewtonRows)
+        return primal_solve_regs<LS::kNV>(nefc, evaluated, cc, gauss, changed);
+    }
+#endif
     const int nv = L.d.nv;
     const T scale = 1 / (o.meaninertia * (T)(nv > 1 ? nv : 1));
     if (!evaluated) {
