@@ -478,12 +478,17 @@ static int launch_untimed(dmc_batch* b, int nstep, int legacy, int mode, void* s
   // pieces of a queued Physics.step(nstep) launch (never with the full stash, whose trailing stage belongs to the last step)
   // (models of more than 16 dofs: the kernels of the small ones are built without the hand-off code, step_core.h kSlices)
   const int slices = (b->geom.queue && b->d_prog && mode == 0 && !b->stash_on && b->tb.L.d.nv > 16) ? std::min(nstep, b->max_slices) : 1;
-  // longest-first hand-out pays for whole items only: with pieces a launch ends within one piece of the last claim whatever
-  // the order (round 6, one box: config 3 +1.4 % without the 16 us ordering kernel in front of every launch, config 4 -0.2 %)
-  if (b->lpt && slices <= 1) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)b->d_cost, b->d_order, b->nitems);
   // a specialisation plugin takes the launch unless it was built lean and the launch needs an optional feature
   const bool need_feat = legacy == 2 || b->d_probe != nullptr || b->tb.opts.integrator == DMC_INT_IMPLICITFAST;
   const bool spec = b->spec_launch && (b->spec_features || !need_feat);
+  // ... but a kernel with a task epilogue (suite/fused_env.py) is the only one that runs the task layer: the library's own
+  // kernel would step the physics and leave observation, reward, flags and step counters as they were, without a word
+  if (b->task_on && mode == 0 && !spec)
+    return fail("the task kernel was built without the optional launch features this launch needs (a substep probe, legacy_step 2 or the "
+                "implicitfast integrator): it cannot take the launch, and no other kernel runs the task layer");
+  // longest-first hand-out pays for whole items only: with pieces a launch ends within one piece of the last claim whatever
+  // the order (round 6, one box: config 3 +1.4 % without the 16 us ordering kernel in front of every launch, config 4 -0.2 %)
+  if (b->lpt && slices <= 1) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)b->d_cost, b->d_order, b->nitems);
   if (b->precision == 64) {
     StepIO<double> io; fill_io(b, &io);
     if (slices > 1) { io.prog = b->d_prog; io.slices = slices; io.cost = nullptr; io.order = nullptr; }
@@ -1194,6 +1199,7 @@ extern "C" int dmc_batch_info(const dmc_batch* b, int* info) {
   info[14] = L.d.njdense; info[15] = L.d.njcon; info[16] = b->stash_on; info[17] = (int)((size_t)L.n_keep * b->elem + (size_t)(L.n_si + 4) * sizeof(int));
   info[18] = (int)((size_t)L.n_gs * b->elem);
   info[19] = b->geom.queue;
+  info[20] = b->geom.queue ? b->max_slices : 0;      // pieces a queued Physics.step(nstep > 1) launch cuts an item into, at most (<= 1: whole items)
   return 0;
 }
 

@@ -6128,7 +6128,8 @@ struct StepCore {
   // en: what entry_issue / entry_commit left for this env and the launch's (mode, legacy)
   // piece / npieces (sliced items of a queued launch, StepIO::slices): this call runs the physics steps
   // [piece * nstep / npieces, (piece + 1) * nstep / npieces) of a mode-0 launch from the state the previous piece stored;
-  // the last piece also runs what ends the launch (the trailing mj_step1, outputs, the kinematic stash).  Every pass
+  // the last piece also runs what ends the launch (the trailing mj_step1, outputs, the kinematic stash) -- and the whole
+  // of an env that the launch override turned into mj_forward.  Every pass
   // rebuilds its derived arrays from (qpos, qvel, act, qacc_warmstart, time), so a cut between the integration of one
   // physics step and the position stage of the next recomputes nothing.
   DMC_DEV void run(const StepIO<T>& io, int env, int nstep, int legacy, int mode, int outmask, int nsub, const Entry& en,
@@ -6141,8 +6142,13 @@ struct StepCore {
       if (em == 1 && (mode == 0 || mode >= 4)) mode = 2;
     }
     if constexpr (!kSlices) { piece = 0; npieces = 1; }
-    if (mode != 0 && piece > 0) return;      // (an env the launch override turned into mj_forward: one pass, in the first piece)
-    if (mode != 0) npieces = 1;
+    // An env the launch override turned into mj_forward makes its ONE pass in the item's LAST piece: the wave that runs
+    // that piece is the one the kernel's task epilogue runs on (step_kernel_body reads the env's arrays from this wave's
+    // LDS slot), so the arrays must be computed here and not by whichever wave claimed piece 0.  The earlier pieces do
+    // nothing (the kernel still publishes the item's progress for them), and the pass loads from the state arrays: no
+    // piece wrote a hand-off record.
+    if (mode != 0 && piece != npieces - 1) return;
+    if (mode != 0) { piece = 0; npieces = 1; }
     if (mode >= 4) { run_split(io, env, mode, outmask, en); return; }
     prof_begin();
     const bool stash = io.stash_r != nullptr;

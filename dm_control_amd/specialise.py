@@ -117,7 +117,8 @@ def path_for(model, precision, lpe, caps, task_header=None):
 def build(model, precision=32, lpe=None, caps=(0, 0, 0), verbose=False, task_header=None):
   """Compiles the plugin for (model, caps = (nconmax, njmax, njcon) as given to the batch, precision, lanes); returns its
   path.  No-op when it is cached.  task_header: a task layer generated by suite/fused_env.py, evaluated by the kernel
-  itself at the end of every step launch (the kernel then holds the optional launch features too)."""
+  itself at the end of every step launch.  (A lean model's kernel leaves the optional launch features out with or without
+  a task: dmc_batch_step refuses a task launch that needs one, since no other kernel runs the task layer.)"""
   lpe = int(lpe or (32 if model.nv <= 12 else 64))
   out = path_for(model, precision, lpe, caps, task_header)
   if os.path.exists(out):

@@ -294,10 +294,10 @@ int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform);
  * the cameras read, did so when the last step / forward launch ran, or no such launch has run yet. */
 int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_dev, void* seg_dev, void* hip_stream);
 
-/* info[0..19] = {B, precision, lanes_per_env, waves_per_block, envs_per_block,
+/* info[0..20] = {B, precision, lanes_per_env, waves_per_block, envs_per_block,
  * lds_bytes_per_block, grid, nconmax, njmax, env_scratch_bytes, static_id,
  * jac_kmax, table_lds_bytes, envs_per_cu, njdense, njcon, stash_on, stash_bytes_per_env,
- * global_scratch_bytes_per_env, work_queue}
+ * global_scratch_bytes_per_env, work_queue, slices}
  * (static_id >= 0: a model-specialised kernel instantiation is in use; jac_kmax: entries per
  * compressed contact Jacobian row; envs_per_cu: environments resident on one CU under the
  * 160 KiB LDS budget; global_scratch_bytes_per_env: what a tree-sparse model (nv > 16) keeps in
@@ -308,7 +308,9 @@ int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_d
  * steps, round by round -- piece s of every environment before piece s + 1 of any; the state travels between pieces
  * through a per-environment hand-off record -- so that the launch ends within one physics step of the last claim
  * instead of within one env-step: trajectories bit-identical, config 4 460 k -> 577 k env-steps/s.  DMC_SLICES=1
- * restores whole items). */
+ * restores whole items); slices: the most pieces such a launch cuts an environment's steps into -- 0 without a work
+ * queue, 1 where the device's L2 arrangement keeps whole items, DMC_SLICES where set.  Models of at most 16 dofs are
+ * never cut). */
 int dmc_batch_info(const dmc_batch* b, int* info);
 
 /* Profiling contract.  Replaces: Physics.enable_profiling() -> wrapper.enable_timer(True), which installs mjcb_time
