@@ -20,7 +20,8 @@ EXPORTS = [
     'dmc_batch_prof_get', 'dmc_gather_create', 'dmc_gather_destroy', 'dmc_gather_run',
     'dmc_batch_set_env_geoms', 'dmc_env_geom_pack', 'dmc_batch_wave_trace', 'dmc_batch_randomize_joints',
     'dmc_batch_attach_specialised', 'dmc_batch_set_task_args', 'dmc_batch_enable_task',
-    'dmc_camera_create', 'dmc_camera_destroy', 'dmc_camera_set_colors', 'dmc_camera_set_tuning', 'dmc_camera_render',
+    'dmc_camera_create', 'dmc_camera_destroy', 'dmc_camera_set_colors', 'dmc_camera_set_materials', 'dmc_camera_set_tuning',
+    'dmc_camera_render',
 ]
 
 _lib = None
@@ -106,6 +107,8 @@ def lib():
     L.dmc_camera_destroy.argtypes = [vp]
     L.dmc_camera_destroy.restype = None
     L.dmc_camera_set_colors.argtypes = [vp, vp, vp]
+    if hasattr(L, 'dmc_camera_set_materials'):      # (absent from a library variant built before the textures: A/B timing)
+      L.dmc_camera_set_materials.argtypes = [vp, vp, vp, ci]
     L.dmc_camera_set_tuning.argtypes = [vp, ci, ci]
     L.dmc_camera_render.argtypes = [vp, ci, vp, vp, vp, vp]
   _lib = L

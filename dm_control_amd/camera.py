@@ -11,8 +11,14 @@ and RGB images of every environment, as torch tensors that never leave the GPU -
   * segmentation: (geom id, 5 = mjOBJ_GEOM), background (-1, -1);
   * RGB: NOT OpenGL.  The geom's colour (geom_rgba, or its material's rgba where the geom's own is MuJoCo's default
     grey) under a headlight at the camera: colour * (ambient + diffuse * max(0, n . -d)), rounded as
-    floor(255 clip(x, 0, 1) + 0.5), over a constant background.  No textures, lights, shadows, reflections, sites,
-    tendons or skybox.
+    floor(255 clip(x, 0, 1) + 0.5), over a constant background.  No lights, shadows, reflections, sites or tendons.
+  * textures (opt-in: `textures`, `materials`, `skybox`, `texture_filter`): the BUILTIN patterns of <texture> -- flat,
+    checker, gradient, with edge / cross marks -- evaluated analytically per pixel on the final hit, texel x colour under
+    the same headlight; 2d textures on planes (texrepeat / texuniform as in mjModel), cube textures on the solids (the
+    face is the largest local coordinate), a flat / gradient skybox where nothing is hit; 'box' filtering takes the exact
+    mean of the pattern over the pixel's footprint on a plane.  The model is PARITY_ASSUMPTIONS.md's, not OpenGL's.
+    File textures are not decoded, `mark="random"` is ignored, and a texture on a geom type it does not map onto keeps
+    the flat colour (`untextured`).  Depth and segmentation never depend on any of this.
   * drawn: plane (front side only, finite where its half-sizes are positive), sphere, capsule, ellipsoid, cylinder,
     box.  Mesh and height-field geoms are scenery the camera does not draw (`skipped_geoms`).  Geoms with alpha 0 and
     geoms whose group is not in `geom_groups` are invisible.  A camera sees the geoms of its own body.
@@ -41,10 +47,123 @@ class _Spec(ctypes.Structure):      # dmc_camera_spec
               ('poscom0', ctypes.c_double * 3), ('mat0', ctypes.c_double * 9), ('fovy', ctypes.c_double)]
 
 
+class _Material(ctypes.Structure):      # dmc_camera_material
+  _fields_ = [('mapping', ctypes.c_int32), ('builtin', ctypes.c_int32), ('mark', ctypes.c_int32), ('width', ctypes.c_int32),
+              ('height', ctypes.c_int32), ('texuniform', ctypes.c_int32), ('has_rgba', ctypes.c_int32), ('reserved', ctypes.c_int32),
+              ('rgb1', ctypes.c_double * 3), ('rgb2', ctypes.c_double * 3), ('markrgb', ctypes.c_double * 3),
+              ('texrepeat', ctypes.c_double * 2), ('rgba', ctypes.c_double * 4)]
+
+
+class _Sky(ctypes.Structure):      # dmc_camera_sky
+  _fields_ = [('builtin', ctypes.c_int32), ('reserved', ctypes.c_int32), ('rgb1', ctypes.c_double * 3), ('rgb2', ctypes.c_double * 3)]
+
+
 class _Options(ctypes.Structure):      # dmc_camera_options
   _fields_ = [('near_m', ctypes.c_double), ('far_m', ctypes.c_double), ('ambient', ctypes.c_double), ('diffuse', ctypes.c_double),
               ('background', ctypes.c_double * 3), ('group_mask', ctypes.c_int32), ('nmat', ctypes.c_int32),
               ('geom_group', ctypes.c_void_p), ('geom_matid', ctypes.c_void_p)]
+
+
+# The suite's floor and sky: the values of the reference's suite/common/materials.xml:8-9 (texture and material `grid`)
+# and suite/common/skybox.xml:3-4, restated as material specs.
+SUITE_GRID = dict(type='2d', builtin='checker', rgb1=(0.1, 0.2, 0.3), rgb2=(0.2, 0.3, 0.4), width=300, height=300, mark='edge',
+                  markrgb=(0.2, 0.3, 0.4), texrepeat=(1.0, 1.0), texuniform=True)
+SUITE_SKYBOX = dict(type='skybox', builtin='gradient', rgb1=(0.4, 0.6, 0.8), rgb2=(0.0, 0.0, 0.0), width=800, height=800,
+                    mark='random', markrgb=(1.0, 1.0, 1.0))
+FILTERS = ('nearest', 'box')
+_SPEC_KEYS = frozenset(('builtin', 'type', 'rgb1', 'rgb2', 'mark', 'markrgb', 'width', 'height', 'texrepeat', 'texuniform', 'rgba'))
+_SPEC_DEFAULTS = dict(type='cube', builtin='none', rgb1=(0.8, 0.8, 0.8), rgb2=(0.5, 0.5, 0.5), mark='none', markrgb=(0.0, 0.0, 0.0),
+                      width=0, height=0, texrepeat=(1.0, 1.0), texuniform=False, rgba=None)
+_DEV_BUILTIN = {'flat': 0, 'checker': 1, 'gradient': 2}      # CAM_TEX_*
+_DEV_MARK = {'none': 0, 'random': 0, 'edge': 1, 'cross': 2}      # CAM_MARK_*
+_TEX_ARRAYS = ('tex_type', 'tex_builtin', 'tex_rgb1', 'tex_rgb2', 'tex_mark', 'tex_markrgb', 'tex_width', 'tex_height', 'tex_file',
+               'mat_texid', 'mat_texrepeat', 'mat_texuniform')
+
+
+def material_spec(spec):
+  """A complete material spec (every key of _SPEC_DEFAULTS) from a user's partial one; ValueError on unknown keys or
+  values."""
+  unknown = set(spec) - _SPEC_KEYS
+  if unknown:
+    raise ValueError('unknown material spec keys: %s' % sorted(unknown))
+  out = dict(_SPEC_DEFAULTS, **spec)
+  for key, allowed in (('type', mjcf_compiler.TEX_TYPES), ('builtin', mjcf_compiler.TEX_BUILTINS), ('mark', mjcf_compiler.TEX_MARKS)):
+    if out[key] not in allowed:
+      raise ValueError('material spec %s=%r: expected one of %s' % (key, out[key], list(allowed)))
+  for key, n in (('rgb1', 3), ('rgb2', 3), ('markrgb', 3), ('texrepeat', 2)):
+    out[key] = tuple(float(v) for v in np.asarray(out[key], dtype=np.float64).reshape(n))
+  if out['rgba'] is not None:
+    out['rgba'] = tuple(float(v) for v in np.asarray(out['rgba'], dtype=np.float64).reshape(4))
+  out['width'], out['height'], out['texuniform'] = int(out['width']), int(out['height']), bool(out['texuniform'])
+  return out
+
+
+def _model_texture(model, t):
+  """Texture t of the model as a spec without the material's keys, and whether its texels come from files."""
+  return dict(type=mjcf_compiler.TEX_TYPES[int(model.tex_type[t])], builtin=mjcf_compiler.TEX_BUILTINS[int(model.tex_builtin[t])],
+              rgb1=tuple(model.tex_rgb1[t]), rgb2=tuple(model.tex_rgb2[t]), mark=mjcf_compiler.TEX_MARKS[int(model.tex_mark[t])],
+              markrgb=tuple(model.tex_markrgb[t]), width=int(model.tex_width[t]), height=int(model.tex_height[t])), bool(model.tex_file[t])
+
+
+def resolve_materials(model, textures=True, materials=None, skybox=None):
+  """What the cameras draw on every geom and in the sky.  textures: use the model's own <texture> / <material>
+  declarations; materials: {geom name or id: spec} overriding or adding per geom; skybox: a spec.  Returns dict(
+  geoms = per geom a complete spec or None (flat colour), sky = a complete spec or None (constant background),
+  untextured = the geoms whose texture is not drawn, reasons = {geom: why}, ignored_marks = who asked for mark="random")."""
+  names = model.names.get('geom', [None] * model.ngeom)
+  label = lambda g: names[g] if names[g] is not None else g
+  geoms, filed = [None] * model.ngeom, [False] * model.ngeom
+  if textures:
+    for g in range(model.ngeom):
+      mat = int(model.geom_matid[g])
+      t = int(model.mat_texid[mat]) if mat >= 0 else -1
+      if t >= 0:
+        tex, filed[g] = _model_texture(model, t)
+        geoms[g] = material_spec(dict(tex, texrepeat=tuple(model.mat_texrepeat[mat]), texuniform=bool(model.mat_texuniform[mat])))
+  for key, spec in (materials or {}).items():
+    g = model.name2id(key, 'geom') if isinstance(key, str) else int(key)
+    if not 0 <= g < model.ngeom:
+      raise ValueError('materials: geom id %d out of range' % g)
+    geoms[g], filed[g] = material_spec(spec), False
+  sky = None
+  if skybox is not None:
+    sky = material_spec(dict(skybox))
+    if sky['builtin'] not in ('gradient', 'flat'):
+      raise ValueError('skybox: builtin must be gradient or flat')
+  elif textures:
+    for t in range(model.ntex):
+      if mjcf_compiler.TEX_TYPES[int(model.tex_type[t])] == 'skybox':
+        tex, from_file = _model_texture(model, t)
+        if not from_file and tex['builtin'] in ('gradient', 'flat'):
+          sky = material_spec(tex)
+        break
+  untextured, reasons, ignored = [], {}, []
+  for g, spec in enumerate(geoms):
+    if spec is None:
+      continue
+    gtype = int(model.geom_type[g])
+    why = None
+    if filed[g]:
+      why = 'file texture'
+    elif gtype not in _DRAWN_TYPES:
+      why = 'mesh / height-field geom'
+    elif spec['type'] == 'skybox':
+      why = 'skybox texture on a geom'
+    elif (spec['type'] == '2d') != (gtype == 0):
+      why = '2d texture on a solid' if spec['type'] == '2d' else 'cube texture on a plane'
+    elif spec['builtin'] == 'none':
+      why = 'no builtin pattern'
+    elif spec['width'] < 1 or (spec['type'] == '2d' and spec['height'] < 1):
+      why = 'texture without a size'
+    if why is not None:
+      untextured.append(label(g))
+      reasons[label(g)] = why
+      geoms[g] = None
+    elif spec['mark'] == 'random':
+      ignored.append(label(g))
+  if sky is not None and sky['mark'] == 'random':
+    ignored.append('skybox')
+  return dict(geoms=geoms, sky=sky, untextured=untextured, reasons=reasons, ignored_marks=ignored)
 
 
 def _body_id(model, body):
@@ -181,7 +300,10 @@ class BatchCamera:
   """
 
   def __init__(self, physics_or_batch, cameras, height, width, near=0.0, far=math.inf, geom_groups=(0, 1, 2), ambient=0.4,
-               diffuse=0.6, background=(0, 0, 0)):
+               diffuse=0.6, background=(0, 0, 0), textures=False, texture_filter='nearest', materials=None, skybox=None):
+    """textures: draw the model's builtin textures and skybox; materials: {geom name or id: spec} and skybox: spec --
+    keys builtin, type, rgb1, rgb2, mark, markrgb, width, height, texrepeat, texuniform, rgba (see `SUITE_GRID`) -- override
+    or add to them, and giving either turns textures on; texture_filter: 'nearest' or 'box'."""
     batch = _find_batch(physics_or_batch, 3)
     if batch is None:
       raise TypeError('BatchCamera needs a BatchedPhysics (or an object holding one as .batch / .physics / .host_physics)')
@@ -227,6 +349,13 @@ class BatchCamera:
       self.output_mask |= {0: OUT['xpos'] | OUT['xmat'], 1: OUT['xpos'], 2: OUT['subtree_com'], 3: OUT['xpos'] | OUT['xmat'],
                            4: OUT['xpos'] | OUT['xmat'] | OUT['subtree_com']}[c['mode']]
     self._colors = None
+    self.untextured, self.untextured_reasons, self.ignored_marks = [], {}, []
+    self.materials, self.sky = [None] * m.ngeom, None      # what is drawn: per geom a complete spec or None; the skybox spec
+    self._tex_request = None
+    if textures or materials is not None or skybox is not None:
+      self.set_materials(materials, skybox, texture_filter, textures=True)
+    elif texture_filter not in FILTERS:
+      raise ValueError('texture_filter must be one of %s' % (FILTERS,))
     self.update_colors()
 
   def close(self):
@@ -240,6 +369,58 @@ class BatchCamera:
     except Exception:  # pylint: disable=broad-except
       pass
 
+  # -- textures -----------------------------------------------------------------------------------------------------
+  def set_materials(self, materials=None, skybox=None, texture_filter='nearest', textures=True):
+    """Turns textures on (see __init__) or, with textures=False and nothing else, off again: renders are then the
+    flat-colour ones, bit for bit.  Like a colour upload this is synchronous and must not happen inside a graph capture."""
+    if texture_filter not in FILTERS:
+      raise ValueError('texture_filter must be one of %s' % (FILTERS,))
+    if not textures and materials is None and skybox is None:
+      self._tex_request = None
+      self.untextured, self.untextured_reasons, self.ignored_marks = [], {}, []
+      self.materials, self.sky = [None] * self.model.ngeom, None
+      _native.check(_native.lib().dmc_camera_set_materials(self._ptr, None, None, 0))
+    else:
+      self._tex_request = dict(textures=bool(textures), materials=dict(materials) if materials is not None else None,
+                               skybox=dict(skybox) if skybox is not None else None, filter=FILTERS.index(texture_filter))
+    self._colors = None      # the next update_colors uploads materials and colours
+    self.update_colors()
+
+  def clear_materials(self):
+    self.set_materials(textures=False)
+
+  def _upload_materials(self):
+    req, m = self._tex_request, self.model
+    res = resolve_materials(m, req['textures'], req['materials'], req['skybox'])
+    self.untextured, self.untextured_reasons, self.ignored_marks = res['untextured'], res['reasons'], res['ignored_marks']
+    log = logging.getLogger(__name__)
+    if self.untextured:
+      log.info('BatchCamera: %d geoms keep their flat colour: %s', len(self.untextured), self.untextured_reasons)
+    if self.ignored_marks:
+      log.info('BatchCamera: mark="random" is ignored: %s', self.ignored_marks)
+    recs = (_Material * max(1, m.ngeom))()
+    for g, spec in enumerate(res['geoms']):
+      if spec is None:
+        continue
+      r = recs[g]
+      r.mapping = 1 if spec['type'] == '2d' else 2
+      r.builtin, r.mark = _DEV_BUILTIN[spec['builtin']], _DEV_MARK[spec['mark']]
+      r.width = spec['width']
+      r.height = (spec['height'] or spec['width']) if spec['type'] == '2d' else spec['width']
+      r.texuniform = int(spec['texuniform'])
+      r.rgb1[:], r.rgb2[:], r.markrgb[:], r.texrepeat[:] = spec['rgb1'], spec['rgb2'], spec['markrgb'], spec['texrepeat']
+      if spec['rgba'] is not None:
+        r.has_rgba = 1
+        r.rgba[:] = spec['rgba']
+    sky = None
+    if res['sky'] is not None:
+      sky = _Sky()
+      sky.builtin = _DEV_BUILTIN[res['sky']['builtin']]
+      sky.rgb1[:], sky.rgb2[:] = res['sky']['rgb1'], res['sky']['rgb2']
+    self.materials, self.sky = res['geoms'], res['sky']
+    _native.check(_native.lib().dmc_camera_set_materials(self._ptr, ctypes.cast(recs, ctypes.c_void_p),
+                                                         ctypes.byref(sky) if sky is not None else None, req['filter']))
+
   # -- colours ------------------------------------------------------------------------------------------------------
   def update_colors(self, force=False):
     """Uploads the model's geom_rgba / mat_rgba if they changed since the last upload (tasks recolour geoms on the host
@@ -251,8 +432,12 @@ class BatchCamera:
     g = np.ascontiguousarray(m.geom_rgba, dtype=np.float64).reshape(-1)
     t = np.ascontiguousarray(m.mat_rgba, dtype=np.float64).reshape(-1)
     key = (g.tobytes(), t.tobytes())
+    if self._tex_request is not None and self._tex_request['textures']:      # the model's textures may be recoloured too
+      key += tuple(np.ascontiguousarray(getattr(m, k)).tobytes() for k in _TEX_ARRAYS)
     if not force and key == self._colors:
       return False
+    if self._tex_request is not None:
+      self._upload_materials()      # (before the colours: a record's own rgba takes effect with the colour upload)
     _native.check(_native.lib().dmc_camera_set_colors(self._ptr, g.ctypes.data if g.size else None, t.ctypes.data if t.size else None))
     self._colors = key
     return True

@@ -1,5 +1,5 @@
 // camera_core.h -- the geometric camera: ray / primitive closed forms in a geom's own frame, surface normals, camera
-// poses and the headlight shading.  Everything here is plain C++ on one pixel or one camera, so that the same text
+// poses, the headlight shading and the analytic textures.  Everything here is plain C++ on one pixel or one camera, so that the same text
 // builds for the device (camera_kernels.hip) and for the host (tests/emu/camera_emu.cpp).
 //
 // The rays are the ones rangefinder sensors cast (step_core.h ray_geom / ray_geom_any: planes front-side only and finite
@@ -276,5 +276,201 @@ struct CamArgs {
 
 int launch_camera_f32(const CamArgs<float>& a, void* stream);
 int launch_camera_f64(const CamArgs<double>& a, void* stream);
+
+// ---- analytic textures ------------------------------------------------------------------------------------------------
+// The builtin patterns are closed-form functions of (u, v); nothing is stored as texels.  A texture has W x H texels and
+// nearest sampling is the ground truth: i = floor(frac(u) W), j = floor(frac(v) H).  Along each axis a texel belongs to
+// one of three classes -- 0 mark, 1 first half (2 i < W), 2 second half -- and the colour depends on the class pair only
+// (the gradient: on the texel), which is what makes the box filter below exact.
+enum { CAM_MAP_NONE = 0, CAM_MAP_PLANE = 1, CAM_MAP_CUBE = 2 };      // how (u, v) comes from the hit point
+enum { CAM_TEX_FLAT = 0, CAM_TEX_CHECKER = 1, CAM_TEX_GRADIENT = 2 };
+enum { CAM_MARK_NONE = 0, CAM_MARK_EDGE = 1, CAM_MARK_CROSS = 2 };
+enum { CAM_FILTER_NEAREST = 0, CAM_FILTER_BOX = 1 };
+
+template <typename T>
+struct CamMat {      // the material of one geom, device form of dmc_camera_material
+  int mapping, builtin, mark, W, H, uniform;
+  T rep[2];
+  float rgb1[3], rgb2[3], markrgb[3];
+};
+
+template <typename T> CAM_DEV T cam_floor(T x);
+template <> CAM_DEV float cam_floor<float>(float x) { return floorf(x); }
+template <> CAM_DEV double cam_floor<double>(double x) { return floor(x); }
+
+template <typename T>
+CAM_DEV int cam_texel_index(T u, int W) {
+  const int i = (int)cam_floor((u - cam_floor(u))*(T)W);
+  return i < 0 ? 0 : (i > W - 1 ? W - 1 : i);      // (frac(u) W can round up to W)
+}
+
+CAM_DEV int cam_texel_class(int i, int W, int mark) {
+  if (mark == CAM_MARK_EDGE && (i == 0 || i == W - 1)) return 0;
+  if (mark == CAM_MARK_CROSS && i == W/2) return 0;
+  return 2*i < W ? 1 : 2;
+}
+
+// smooth step of the distance of texel (i, j)'s centre from the middle of the texture, in [-1, 1]^2
+template <typename T>
+CAM_DEV T cam_gradient_step(int i, int j, int W, int H) {
+  const T x = (T)(2*i + 1)/(T)W - 1, y = (T)(2*j + 1)/(T)H - 1;
+  T p = cam_sqrt(x*x + y*y);
+  p = p > 1 ? (T)1 : p;
+  return p*p*(3 - 2*p);
+}
+
+// colour of the class pair (cu, cv); gs: the gradient's step at the texel
+template <typename T>
+CAM_DEV void cam_pair_color(const CamMat<T>& m, int cu, int cv, T gs, T* out) {
+  for (int k = 0; k < 3; k++) {
+    if (cu == 0 || cv == 0) out[k] = (T)m.markrgb[k];
+    else if (m.builtin == CAM_TEX_GRADIENT) out[k] = (T)m.rgb1[k] + ((T)m.rgb2[k] - (T)m.rgb1[k])*gs;
+    else out[k] = (T)(m.builtin == CAM_TEX_CHECKER && cu != cv ? m.rgb2[k] : m.rgb1[k]);
+  }
+}
+
+template <typename T>
+CAM_DEV void cam_texel(const CamMat<T>& m, T u, T v, float* out) {
+  const int i = cam_texel_index(u, m.W), j = cam_texel_index(v, m.H);
+  T c[3];
+  cam_pair_color(m, cam_texel_class(i, m.W, m.mark), cam_texel_class(j, m.H, m.mark),
+                 m.builtin == CAM_TEX_GRADIENT ? cam_gradient_step<T>(i, j, m.W, m.H) : (T)0, c);
+  for (int k = 0; k < 3; k++) out[k] = (float)c[k];
+}
+
+// integral over [0, x] of the 1-periodic indicator of [a, b), 0 <= a <= b <= 1: whole periods plus the clamped remainder
+template <typename T>
+CAM_DEV T cam_periodic_integral(T x, T a, T b) {
+  const T n = cam_floor(x), f = x - n;
+  return n*(b - a) + (f < a ? (T)0 : (f > b ? b : f) - a);
+}
+template <typename T>
+CAM_DEV T cam_interval_share(T x0, T x1, T a, T b) {
+  return (cam_periodic_integral(x1, a, b) - cam_periodic_integral(x0, a, b))/(x1 - x0);
+}
+
+// the exact shares w[0..2] of [u - h, u + h] that fall into the three classes of a W-texel axis; h <= 0: the texel at u
+template <typename T>
+CAM_DEV void cam_class_shares(T u, T h, int W, int mark, T* w) {
+  if (!(h > 0)) {
+    const int c = cam_texel_class(cam_texel_index(u, W), W, mark);
+    w[0] = c == 0; w[1] = c == 1; w[2] = c == 2;
+    return;
+  }
+  T a0 = 0, b0 = 0, a1 = 0, b1 = 0;      // the mark's texels: at most two intervals of [0, 1)
+  if (mark == CAM_MARK_EDGE) { b0 = (T)1/(T)W; if (W > 1) { a1 = (T)(W - 1)/(T)W; b1 = 1; } }
+  else if (mark == CAM_MARK_CROSS) { a0 = (T)(W/2)/(T)W; b0 = (T)(W/2 + 1)/(T)W; }
+  const T hb = (T)((W + 1)/2)/(T)W;      // the first half ends where 2 i < W does
+  const T x0 = u - h, x1 = u + h;
+  w[0] = cam_interval_share(x0, x1, a0, b0) + cam_interval_share(x0, x1, a1, b1);
+  w[1] = cam_interval_share(x0, x1, (T)0, hb) - cam_interval_share(x0, x1, a0 < hb ? a0 : hb, b0 < hb ? b0 : hb)
+       - cam_interval_share(x0, x1, a1 < hb ? a1 : hb, b1 < hb ? b1 : hb);
+  w[2] = 1 - w[0] - w[1];
+}
+
+// box filter: the mean of the nearest-sampled pattern over the uv box (u -+ hu, v -+ hv), as the sum over the 3 x 3 class
+// pairs of share_u share_v colour(pair).  The gradient is evaluated at the centre.
+template <typename T>
+CAM_DEV void cam_texel_box(const CamMat<T>& m, T u, T v, T hu, T hv, float* out) {
+  T wu[3], wv[3], acc[3] = {0, 0, 0};
+  cam_class_shares(u, hu, m.W, m.mark, wu);
+  cam_class_shares(v, hv, m.H, m.mark, wv);
+  const T gs = m.builtin == CAM_TEX_GRADIENT ? cam_gradient_step<T>(cam_texel_index(u, m.W), cam_texel_index(v, m.H), m.W, m.H) : (T)0;
+  for (int cu = 0; cu < 3; cu++) for (int cv = 0; cv < 3; cv++) {
+    T c[3];
+    cam_pair_color(m, cu, cv, gs, c);
+    for (int k = 0; k < 3; k++) acc[k] += wu[cu]*wv[cv]*c[k];
+  }
+  for (int k = 0; k < 3; k++) out[k] = (float)acc[k];
+}
+
+// 2d texture on a plane: (u, v) of the hit point (px, py) in the plane's frame and the scales du/dpx, dv/dpy
+template <typename T>
+CAM_DEV void cam_plane_uv(const CamMat<T>& m, const T* size, T px, T py, T* uv, T* scale) {
+  if (m.uniform) { scale[0] = m.rep[0]; scale[1] = m.rep[1]; uv[0] = px*m.rep[0]; uv[1] = py*m.rep[1]; return; }
+  const T sx = size[0] > 0 ? size[0] : (T)1, sy = size[1] > 0 ? size[1] : (T)1;
+  scale[0] = m.rep[0]/(2*sx); scale[1] = m.rep[1]/(2*sy);
+  uv[0] = m.rep[0]*(px/(2*sx) + (T)0.5); uv[1] = m.rep[1]*(py/(2*sy) + (T)0.5);
+}
+
+// Half-widths (in the plane's x and y) of a pixel's footprint, 0.5 (|dp/dcol| + |dp/drow|), from the closed-form
+// derivative of the ray / plane intersection p = lp - (lp_z / lv_z) lv with respect to the pixel direction:
+// lv = M (dx, dy, -1), d(dx)/d(col) = inv_f, d(dy)/d(row) = -inv_f.
+template <typename T>
+CAM_DEV void cam_plane_footprint(const T* lp, const T* lv, const T* M, T inv_f, T* half) {
+  const T s = -lp[2]/(lv[2]*lv[2])*inv_f;
+  for (int k = 0; k < 2; k++) {
+    const T dc = s*(M[3*k]*lv[2] - lv[k]*M[6]), dr = s*(M[3*k + 1]*lv[2] - lv[k]*M[7]);
+    half[k] = (T)0.5*(cam_abs(dc) + cam_abs(dr));
+  }
+}
+
+// cube texture on a solid: the face is the largest |component| of the local hit point q (divided by the half-extents
+// unless texuniform), lowest axis on ties; the other two components in cyclic order, over |q_face|, go to [0, 1] x repeat
+template <typename T>
+CAM_DEV int cam_cube_uv(const CamMat<T>& m, int type, const T* size, const T* p, T* uv) {
+  T q[3] = {p[0], p[1], p[2]};
+  if (!m.uniform) {
+    const bool round = type == DMC_GEOM_SPHERE || type == DMC_GEOM_CAPSULE || type == DMC_GEOM_CYLINDER;
+    const T ex = size[0], ey = round ? size[0] : size[1];
+    const T ez = type == DMC_GEOM_SPHERE ? size[0] : type == DMC_GEOM_CAPSULE ? size[0] + size[1] : type == DMC_GEOM_CYLINDER ? size[1] : size[2];
+    q[0] /= ex; q[1] /= ey; q[2] /= ez;
+  }
+  const T a0 = cam_abs(q[0]), a1 = cam_abs(q[1]), a2 = cam_abs(q[2]);
+  int face = a1 > a0 ? 1 : 0;
+  if (a2 > (face ? a1 : a0)) face = 2;
+  const T den = face == 0 ? a0 : face == 1 ? a1 : a2;
+  const T s = face == 0 ? q[1] : face == 1 ? q[2] : q[0], t = face == 0 ? q[2] : face == 1 ? q[0] : q[1];
+  const bool ok = den >= (T)DMC_MINVAL;
+  uv[0] = m.rep[0]*(T)0.5*((ok ? s/den : (T)0) + 1);
+  uv[1] = m.rep[1]*(T)0.5*((ok ? t/den : (T)0) + 1);
+  return face;
+}
+
+// texel colour at the final hit of a pixel (white where the material maps nothing onto this geom type).  M = Rg' Rcam of
+// the hit geom and inv_f are read only under the box filter on a plane.
+template <typename T>
+CAM_DEV void cam_texture(const CamMat<T>& m, const CamHit<T>& h, const T* M, T inv_f, int filter, float* out) {
+  out[0] = 1; out[1] = 1; out[2] = 1;
+  const T p[3] = {h.lp[0] + h.t*h.lv[0], h.lp[1] + h.t*h.lv[1], h.lp[2] + h.t*h.lv[2]};
+  T uv[2];
+  if (m.mapping == CAM_MAP_PLANE && h.type == DMC_GEOM_PLANE) {
+    T scale[2];
+    cam_plane_uv(m, h.size, p[0], p[1], uv, scale);
+    if (filter == CAM_FILTER_BOX) {
+      T half[2];
+      cam_plane_footprint(h.lp, h.lv, M, inv_f, half);
+      cam_texel_box(m, uv[0], uv[1], cam_abs(scale[0])*half[0], cam_abs(scale[1])*half[1], out);
+    } else cam_texel(m, uv[0], uv[1], out);
+  } else if (m.mapping == CAM_MAP_CUBE && h.type != DMC_GEOM_PLANE) {
+    cam_cube_uv(m, h.type, h.size, p, uv);
+    cam_texel(m, uv[0], uv[1], out);
+  }
+}
+
+template <typename T>
+CAM_DEV uint8_t cam_round8(T v) {
+  v = v < 0 ? (T)0 : (v > 1 ? (T)1 : v);
+  return (uint8_t)(int)floor((double)(255*v + (T)0.5));
+}
+
+// skybox: the smooth step of p = (1 - w_z) / 2 between rgb1 (zenith) and rgb2 (nadir), w the unit world direction of
+// the ray; unshaded
+template <typename T>
+CAM_DEV void cam_sky(const float* rgb1, const float* rgb2, int builtin, const T* R, T dx, T dy, uint8_t* out) {
+  const T wz = (R[6]*dx + R[7]*dy - R[8])/cam_sqrt(dx*dx + dy*dy + 1);
+  const T p = (T)0.5*(1 - wz), s = builtin == CAM_TEX_GRADIENT ? p*p*(3 - 2*p) : (T)0;
+  for (int k = 0; k < 3; k++) out[k] = cam_round8((T)rgb1[k] + ((T)rgb2[k] - (T)rgb1[k])*s);
+}
+
+template <typename T>
+struct CamTexArgs {      // what a render with textures reads beside CamArgs
+  const CamMat<T>* mat;      // (ngeom)
+  int filter, sky;           // CAM_FILTER_*; sky: 0 constant background, else 1 + CAM_TEX_FLAT / CAM_TEX_GRADIENT
+  float sky1[3], sky2[3];
+};
+
+int launch_camera_tex_f32(const CamArgs<float>& a, const CamTexArgs<float>& t, void* stream);
+int launch_camera_tex_f64(const CamArgs<double>& a, const CamTexArgs<double>& t, void* stream);
 
 }  // namespace dmc

@@ -15,8 +15,10 @@ namespace dmc {
 
 // kPre = false: the tuning study's kernel without the pre-transform (an instantiation of its own, so that the production
 // kernel's registers do not pay for it)
-template <typename T, bool kPre>
-__global__ void __launch_bounds__(kCamTile) camera_kernel(const CamArgs<T> a) {
+// kTex = true: textures and skybox in the shading stage, again an instantiation of its own: the kTex = false kernel never
+// reads `t` and is the flat-colour kernel instruction for instruction
+template <typename T, bool kPre, bool kTex>
+__global__ void __launch_bounds__(kCamTile) camera_kernel(const CamArgs<T> a, const CamTexArgs<T> t) {
   __shared__ CamGeom<T> s_geom[kCamTile];
   __shared__ T s_cam[12];
   __shared__ int s_cnt[kCamTile/64 + 1];
@@ -97,21 +99,47 @@ __global__ void __launch_bounds__(kCamTile) camera_kernel(const CamArgs<T> a) {
   if (a.seg) { a.seg[2*o] = h.id; a.seg[2*o + 1] = h.id >= 0 ? kCamObjGeom : -1; }
   if (a.rgb) {
     uint8_t px[3] = {a.bg[0], a.bg[1], a.bg[2]};
-    if (h.id >= 0) cam_shade(h, dx, dy, a.geom_color + 3*h.id, a.ambient, a.diffuse, px);
+    if (!kTex) {
+      if (h.id >= 0) cam_shade(h, dx, dy, a.geom_color + 3*h.id, a.ambient, a.diffuse, px);
+    } else if (h.id >= 0) {
+      // once per pixel, on the final hit: texel x the geom's colour goes through the same shade and rounding
+      const CamMat<T> m = t.mat[h.id];
+      float col[3] = {a.geom_color[3*h.id], a.geom_color[3*h.id + 1], a.geom_color[3*h.id + 2]};
+      if (m.mapping != CAM_MAP_NONE) {
+        T M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (t.filter == CAM_FILTER_BOX && m.mapping == CAM_MAP_PLANE) {      // M = Rg' Rcam of the hit geom, for the footprint
+          T gm[9];
+          for (int k = 0; k < 9; k++) gm[k] = a.geom_xmat[(size_t)(9*h.id + k)*B + env];
+          for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[3*i + j] = gm[i]*R[j] + gm[3 + i]*R[3 + j] + gm[6 + i]*R[6 + j];
+        }
+        float tex[3];
+        cam_texture(m, h, M, c.inv_f, t.filter, tex);
+        for (int k = 0; k < 3; k++) col[k] *= tex[k];
+      }
+      cam_shade(h, dx, dy, col, a.ambient, a.diffuse, px);
+    } else if (t.sky) cam_sky(t.sky1, t.sky2, t.sky - 1, R, dx, dy, px);
     for (int k = 0; k < 3; k++) a.rgb[3*o + k] = px[k];
   }
 }
 
-template <typename T>
-static int launch_camera(const CamArgs<T>& a, void* stream) {
+template <typename T, bool kTex>
+static int launch_camera(const CamArgs<T>& a, const CamTexArgs<T>& t, void* stream) {
   const int ntile = (a.H*a.W + kCamTile - 1)/kCamTile;
   const long long grid = (long long)a.B*a.ncam*ntile;
   if (grid <= 0 || grid > 0x7fffffffLL) return -1;
-  if (a.pretransform) hipLaunchKernelGGL((camera_kernel<T, true>), dim3((unsigned)grid), dim3(kCamTile), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((camera_kernel<T, false>), dim3((unsigned)grid), dim3(kCamTile), 0, (hipStream_t)stream, a);
+  if (a.pretransform) hipLaunchKernelGGL((camera_kernel<T, true, kTex>), dim3((unsigned)grid), dim3(kCamTile), 0, (hipStream_t)stream, a, t);
+  else hipLaunchKernelGGL((camera_kernel<T, false, kTex>), dim3((unsigned)grid), dim3(kCamTile), 0, (hipStream_t)stream, a, t);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-int launch_camera_f32(const CamArgs<float>& a, void* stream) { return launch_camera(a, stream); }
-int launch_camera_f64(const CamArgs<double>& a, void* stream) { return launch_camera(a, stream); }
+int launch_camera_f32(const CamArgs<float>& a, void* stream) { return launch_camera<float, false>(a, CamTexArgs<float>{}, stream); }
+int launch_camera_f64(const CamArgs<double>& a, void* stream) { return launch_camera<double, false>(a, CamTexArgs<double>{}, stream); }
+int launch_camera_tex_f32(const CamArgs<float>& a, const CamTexArgs<float>& t, void* stream) {
+  if (!t.mat) return -3;
+  return launch_camera<float, true>(a, t, stream);
+}
+int launch_camera_tex_f64(const CamArgs<double>& a, const CamTexArgs<double>& t, void* stream) {
+  if (!t.mat) return -3;
+  return launch_camera<double, true>(a, t, stream);
+}
 
 }  // namespace dmc

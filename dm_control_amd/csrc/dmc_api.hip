@@ -1428,6 +1428,10 @@ struct dmc_camera {
   double near_, far_, ambient, diffuse, bg[3];
   std::vector<int> matid;
   void* d_cams; int* d_type; int* d_skip; float* d_color;
+  // textures (dmc_camera_set_materials): off until set, and off again when cleared
+  int tex_on, tex_filter, sky; float sky1[3], sky2[3];
+  void* d_mat;      // CamMat<T>[ngeom] in the batch precision
+  std::vector<double> mat_rgba_own;      // (ngeom, 4): a material record's own rgba, NaN where it has none
   int f_gpos, f_gmat, f_xpos, f_xmat, f_com;      // field indices
 };
 template <typename T>
@@ -1475,6 +1479,7 @@ extern "C" int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* 
   c->f_gpos = b->index["geom_xpos"]; c->f_gmat = b->index["geom_xmat"]; c->f_xpos = b->index["xpos"];
   c->f_xmat = b->index["xmat"]; c->f_com = b->index["subtree_com"];
   c->d_cams = nullptr; c->d_type = nullptr; c->d_skip = nullptr; c->d_color = nullptr;
+  c->d_mat = nullptr; c->tex_on = 0; c->tex_filter = 0; c->sky = 0;
   hipError_t e = hipSetDevice(b->device);
   const size_t ni = sizeof(int)*type.size();
   if (e == hipSuccess) e = hipMalloc((void**)&c->d_type, ni);
@@ -1506,6 +1511,7 @@ extern "C" void dmc_camera_destroy(dmc_camera* c) {
   if (c->d_type) (void)hipFree(c->d_type);
   if (c->d_skip) (void)hipFree(c->d_skip);
   if (c->d_color) (void)hipFree(c->d_color);
+  if (c->d_mat) (void)hipFree(c->d_mat);
   delete c;
 }
 extern "C" int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, const double* mat_rgba) {
@@ -1514,11 +1520,61 @@ extern "C" int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, con
   for (int g = 0; g < c->ngeom; g++) {
     const double* s = geom_rgba + 4*g;
     // mjv's setMaterial: a material's colour takes over only where the geom's own rgba is the default grey
-    if (c->matid[g] >= 0 && mat_rgba && s[0] == 0.5 && s[1] == 0.5 && s[2] == 0.5 && s[3] == 1.0) s = mat_rgba + 4*c->matid[g];
+    const bool grey = s[0] == 0.5 && s[1] == 0.5 && s[2] == 0.5 && s[3] == 1.0;
+    if (grey && c->tex_on && !c->mat_rgba_own.empty() && c->mat_rgba_own[4*g] == c->mat_rgba_own[4*g]) s = &c->mat_rgba_own[4*g];
+    else if (c->matid[g] >= 0 && mat_rgba && grey) s = mat_rgba + 4*c->matid[g];
     for (int k = 0; k < 3; k++) col[3*g + k] = (float)s[k];
   }
   HIP_TRY(hipSetDevice(c->b->device));
   HIP_TRY(hipMemcpy(c->d_color, col.data(), sizeof(float)*col.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+template <typename T>
+static int upload_materials(dmc_camera* c, const dmc_camera_material* mats) {
+  std::vector<CamMat<T>> d((size_t)std::max(1, c->ngeom));
+  memset(d.data(), 0, sizeof(d[0])*d.size());
+  for (int g = 0; g < c->ngeom; g++) {
+    const dmc_camera_material& s = mats[g];
+    CamMat<T>& m = d[g];
+    m.mapping = s.mapping; m.builtin = s.builtin; m.mark = s.mark; m.W = s.width; m.H = s.height; m.uniform = s.texuniform ? 1 : 0;
+    for (int k = 0; k < 2; k++) m.rep[k] = (T)s.texrepeat[k];
+    for (int k = 0; k < 3; k++) { m.rgb1[k] = (float)s.rgb1[k]; m.rgb2[k] = (float)s.rgb2[k]; m.markrgb[k] = (float)s.markrgb[k]; }
+  }
+  if (!c->d_mat) HIP_TRY(hipMalloc(&c->d_mat, sizeof(d[0])*d.size()));
+  HIP_TRY(hipMemcpy(c->d_mat, d.data(), sizeof(d[0])*d.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+extern "C" int dmc_camera_set_materials(dmc_camera* c, const dmc_camera_material* per_geom, const dmc_camera_sky* sky, int filter) {
+  if (!c) return fail("null camera");
+  if (filter != CAM_FILTER_NEAREST && filter != CAM_FILTER_BOX) return fail("camera materials: filter must be 0 (nearest) or 1 (box)");
+  if (!per_geom && !sky) {      // cleared: the next render launches the flat-colour kernel again
+    c->tex_on = 0; c->sky = 0; c->mat_rgba_own.clear();
+    return 0;
+  }
+  const HostModel& hm = c->b->model->hm;
+  std::vector<dmc_camera_material> none;
+  if (!per_geom) { none.assign((size_t)std::max(1, c->ngeom), dmc_camera_material()); per_geom = none.data(); }
+  for (int g = 0; g < c->ngeom; g++) {
+    const dmc_camera_material& s = per_geom[g];
+    if (s.mapping < CAM_MAP_NONE || s.mapping > CAM_MAP_CUBE) return fail("camera materials: mapping out of range");
+    if (s.mapping == CAM_MAP_NONE) continue;
+    if (s.builtin < CAM_TEX_FLAT || s.builtin > CAM_TEX_GRADIENT) return fail("camera materials: builtin out of range");
+    if (s.mark < CAM_MARK_NONE || s.mark > CAM_MARK_CROSS) return fail("camera materials: mark out of range");
+    if (s.width < 1 || s.height < 1 || s.width > (1 << 24) || s.height > (1 << 24)) return fail("camera materials: a texture needs 1 <= width, height <= 2^24 texels");
+    const int type = hm.geom_type[g];
+    if ((s.mapping == CAM_MAP_PLANE) != (type == DMC_GEOM_PLANE)) return fail("camera materials: a 2d texture maps onto planes and a cube texture onto solids only");
+    if (s.mapping == CAM_MAP_CUBE && type != DMC_GEOM_SPHERE && type != DMC_GEOM_CAPSULE && type != DMC_GEOM_ELLIPSOID &&
+        type != DMC_GEOM_CYLINDER && type != DMC_GEOM_BOX) return fail("camera materials: a cube texture on a geom the camera does not draw");
+  }
+  if (sky && (sky->builtin != CAM_TEX_FLAT && sky->builtin != CAM_TEX_GRADIENT)) return fail("camera materials: the skybox is flat or gradient");
+  HIP_TRY(hipSetDevice(c->b->device));
+  const int rc = c->b->precision == 64 ? upload_materials<double>(c, per_geom) : upload_materials<float>(c, per_geom);
+  if (rc) return rc;
+  c->mat_rgba_own.assign(4*(size_t)std::max(1, c->ngeom), (double)NAN);
+  for (int g = 0; g < c->ngeom; g++) if (per_geom[g].has_rgba) for (int k = 0; k < 4; k++) c->mat_rgba_own[4*g + k] = per_geom[g].rgba[k];
+  c->sky = sky ? 1 + sky->builtin : 0;
+  for (int k = 0; k < 3; k++) { c->sky1[k] = sky ? (float)sky->rgb1[k] : 0.f; c->sky2[k] = sky ? (float)sky->rgb2[k] : 0.f; }
+  c->tex_filter = filter; c->tex_on = 1;
   return 0;
 }
 extern "C" int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform) {
@@ -1529,6 +1585,8 @@ extern "C" int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform) 
 }
 static int launch_cam(const CamArgs<float>& a, void* s) { return launch_camera_f32(a, s); }
 static int launch_cam(const CamArgs<double>& a, void* s) { return launch_camera_f64(a, s); }
+static int launch_cam_tex(const CamArgs<float>& a, const CamTexArgs<float>& t, void* s) { return launch_camera_tex_f32(a, t, s); }
+static int launch_cam_tex(const CamArgs<double>& a, const CamTexArgs<double>& t, void* s) { return launch_camera_tex_f64(a, t, s); }
 template <typename T>
 static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void* seg, void* stream) {
   dmc_batch* b = c->b;
@@ -1550,7 +1608,13 @@ static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void
   a.bg[3] = 0;
   a.rgb = (what & CAM_RGB) ? (uint8_t*)rgb : nullptr; a.depth = (what & CAM_DEPTH) ? (T*)depth : nullptr;
   a.seg = (what & CAM_SEG) ? (int*)seg : nullptr;
-  const int rc = launch_cam(a, stream);
+  int rc;
+  if (c->tex_on) {
+    CamTexArgs<T> t;
+    t.mat = (const CamMat<T>*)c->d_mat; t.filter = c->tex_filter; t.sky = c->sky;
+    for (int k = 0; k < 3; k++) { t.sky1[k] = c->sky1[k]; t.sky2[k] = c->sky2[k]; }
+    rc = launch_cam_tex(a, t, stream);
+  } else rc = launch_cam(a, stream);
   if (rc) return fail(rc == -1 ? "camera render: the launch grid does not fit" : "camera render: launch failed", -2);
   return 0;
 }

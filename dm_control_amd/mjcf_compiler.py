@@ -35,6 +35,9 @@ MINVAL = C['DMC_MINVAL']
 _JNT = {'free': 0, 'ball': 1, 'slide': 2, 'hinge': 3}
 _GEOM = {'plane': 0, 'hfield': 1, 'sphere': 2, 'capsule': 3, 'ellipsoid': 4,
          'cylinder': 5, 'box': 6, 'mesh': 7}
+TEX_TYPES = ('2d', 'cube', 'skybox')      # mjtTexture
+TEX_BUILTINS = ('none', 'gradient', 'checker', 'flat')      # mjtBuiltin
+TEX_MARKS = ('none', 'edge', 'cross', 'random')      # mjtMark
 _DISABLE_FLAGS = ['constraint', 'equality', 'frictionloss', 'limit', 'contact',
                   'spring', 'damper', 'gravity', 'clampctrl', 'warmstart',
                   'filterparent', 'actuation', 'refsafe', 'sensor', 'midphase',
@@ -997,11 +1000,25 @@ class _Compiler:
     # material alpha: rays (rangefinder sensors) skip invisible geoms (rgba alpha 0, or a material with alpha 0)
     self.material_alpha = {}
     self.materials = []
+    self.material_tex = []
+    self.textures = []
     for asset in self.root.findall('asset'):
       for mat in asset.findall('material'):
         rgba = _vec(mat.get('rgba', '1 1 1 1'))
         self.material_alpha[mat.get('name')] = float(rgba[3]) if rgba.size == 4 else 1.0
         self.materials.append((mat.get('name'), rgba if rgba.size == 4 else np.ones(4)))
+        self.material_tex.append(dict(texture=mat.get('texture'), texrepeat=_vec(mat.get('texrepeat', '1 1'), 2),
+                                      texuniform=int(mat.get('texuniform', 'false') == 'true')))
+      for tex in asset.findall('texture'):
+        # builtin textures are closed-form patterns the ray-cast cameras evaluate (camera.py); file textures are not decoded
+        filed = any(k.startswith('file') for k in tex.attrib)
+        for key, allowed in (('type', TEX_TYPES), ('builtin', TEX_BUILTINS), ('mark', TEX_MARKS)):
+          if tex.get(key, allowed[0] if key != 'type' else 'cube') not in allowed:
+            raise MjcfError('texture %s=%r: expected one of %s' % (key, tex.get(key), list(allowed)))
+        self.textures.append(dict(type=TEX_TYPES.index(tex.get('type', 'cube')), builtin=TEX_BUILTINS.index(tex.get('builtin', 'none')),
+                                  rgb1=_vec(tex.get('rgb1', '0.8 0.8 0.8'), 3), rgb2=_vec(tex.get('rgb2', '0.5 0.5 0.5'), 3),
+                                  mark=TEX_MARKS.index(tex.get('mark', 'none')), markrgb=_vec(tex.get('markrgb', '0 0 0'), 3),
+                                  width=int(tex.get('width', 0)), height=int(tex.get('height', 0)), file=int(filed)))
       for mesh in asset.findall('mesh'):
         f = mesh.get('file')
         if f:
@@ -1206,6 +1223,26 @@ class _Compiler:
                            texture=named(assets, 'texture'), numeric=named(custom, 'numeric'), text=named(custom, 'text'),
                            tuple=named(custom, 'tuple'))
     m.nmesh, m.nhfield, m.ntex = (len(self._aux_names[k]) for k in ('mesh', 'hfield', 'texture'))
+    # textures and what materials say about them: host-side arrays the ray-cast cameras read (camera.py).  tex_type /
+    # tex_builtin / tex_mark index TEX_TYPES / TEX_BUILTINS / TEX_MARKS; tex_file marks a texture whose texels come from
+    # files, which nothing here decodes
+    tx = self.textures
+    m.tex_type = np.array([t['type'] for t in tx], dtype=np.int64)
+    m.tex_builtin = np.array([t['builtin'] for t in tx], dtype=np.int64)
+    m.tex_mark = np.array([t['mark'] for t in tx], dtype=np.int64)
+    m.tex_rgb1 = np.array([t['rgb1'] for t in tx], dtype=np.float64).reshape(m.ntex, 3)
+    m.tex_rgb2 = np.array([t['rgb2'] for t in tx], dtype=np.float64).reshape(m.ntex, 3)
+    m.tex_markrgb = np.array([t['markrgb'] for t in tx], dtype=np.float64).reshape(m.ntex, 3)
+    m.tex_width = np.array([t['width'] for t in tx], dtype=np.int64)
+    m.tex_height = np.array([t['height'] for t in tx], dtype=np.int64)
+    m.tex_file = np.array([t['file'] for t in tx], dtype=np.int64)
+    tex_names = self._aux_names['texture']
+    for mt in self.material_tex:
+      if mt['texture'] is not None and mt['texture'] not in tex_names:
+        raise MjcfError('material texture %r is not a texture of the model' % (mt['texture'],))
+    m.mat_texid = np.array([tex_names.index(mt['texture']) if mt['texture'] is not None else -1 for mt in self.material_tex], dtype=np.int64)
+    m.mat_texrepeat = np.array([mt['texrepeat'] for mt in self.material_tex], dtype=np.float64).reshape(m.nmat, 2)
+    m.mat_texuniform = np.array([mt['texuniform'] for mt in self.material_tex], dtype=np.int64)
     m.nnumeric, m.ntext, m.ntuple = (len(self._aux_names[k]) for k in ('numeric', 'text', 'tuple'))
     # <custom><numeric>: host-side constants tasks read by name (mujoco/index.py:93-99 'nnumericdata'); `size` pads with zeros
     nums = []

@@ -625,7 +625,7 @@ class _DirAssets(dict):
     return (dict, (dict(self),))
 
 
-_MJB_MAGIC = b'DMCMJB01'
+_MJB_MAGIC = b'DMCMJB02'      # 02: the compiled model carries the texture arrays (tex_*, mat_tex*)
 
 
 def _dump_mjb(m):

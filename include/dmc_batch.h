@@ -282,6 +282,29 @@ void dmc_camera_destroy(dmc_camera* c);
  * episodes): geom_rgba (ngeom, 4) and mat_rgba (nmat, 4) or NULL.  A material's colour replaces a geom's own only
  * where that is MuJoCo's default (0.5, 0.5, 0.5, 1).  Synchronous. */
 int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, const double* mat_rgba);
+/* Builtin textures and the skybox, evaluated analytically in the shading stage (no texels are stored; file textures are
+ * not decoded).  Replaces what mjr_render draws from mjModel's tex_* / mat_tex* arrays (mjr_uploadTexture and
+ * mjv_updateScene's material lookup; engine.py:840-870).  This project's documented model, not OpenGL's.
+ * One record per geom.  mapping: 0 none (the flat colour), 1 a 2d texture on a plane geom, 2 a cube texture on a sphere,
+ * capsule, ellipsoid, cylinder or box.  builtin: 0 flat, 1 checker (2 x 2), 2 gradient.  mark: 0 none, 1 edge, 2 cross.
+ * width x height texels (every cube face is width x width: pass height = width).  texrepeat / texuniform as in
+ * mjModel.  has_rgba: `rgba` is the material's colour, drawn where the geom's own rgba is MuJoCo's default grey (it
+ * takes effect with the next dmc_camera_set_colors).  The texel multiplies the geom's colour before the headlight. */
+typedef struct dmc_camera_material {
+  int32_t mapping, builtin, mark, width, height, texuniform, has_rgba, reserved;
+  double rgb1[3], rgb2[3], markrgb[3], texrepeat[2], rgba[4];
+} dmc_camera_material;
+/* Skybox for pixels that hit nothing: builtin 0 flat (rgb1) or 2 gradient -- rgb1 at the zenith to rgb2 at the nadir
+ * by the smooth step of (1 - w_z) / 2, w the unit world direction of the ray; unshaded. */
+typedef struct dmc_camera_sky {
+  int32_t builtin, reserved;
+  double rgb1[3], rgb2[3];
+} dmc_camera_sky;
+/* per_geom: (ngeom) records or NULL (no geom is textured); sky or NULL (the constant background stays); filter: 0
+ * nearest, 1 box (2d textures on planes: the exact mean of the pattern over the pixel's footprint in uv).  Both NULL
+ * clears: renders are the flat-colour ones again, and dmc_camera_render launches what it did before the first call.
+ * Synchronous, like the colour upload; call dmc_camera_set_colors afterwards where a record carries an rgba. */
+int dmc_camera_set_materials(dmc_camera* c, const dmc_camera_material* per_geom, const dmc_camera_sky* sky_or_null, int filter);
 /* Tuning study switches, both on by default.  cull: geoms whose bounding sphere misses a pixel tile are dropped before
  * staging.  pretransform: the staged geoms hold the ray origin and the camera rotation in the geom's frame (off: the
  * world frame, transformed per pixel). */
