@@ -3078,6 +3078,10 @@ struct StepCore {
   }
   DMC_DEV void rne_post_constraint() {
     const int nb = L.d.nbody, ncon = SI(imisc)[IM_NCON];
+    // cacc / cfrc / cfrc_ext share their memory with the solver's vectors (step_layout.h: the VEL and SOL overlays start at
+    // one base): a damped solve the acceleration stage left in sv_Mgrad for mj_Euler does not survive this pass, so
+    // euler_state solves for itself
+    if constexpr (kAccRegs) { if (lane == 0) S(misc)[kMiscEulerSolved] = 0; }
     // external (contact) wrench per body, contacts visited in index order
     FOR_LANES(b, nb) {
       T acc[6] = {0, 0, 0, 0, 0, 0};
@@ -5333,7 +5337,7 @@ struct StepCore {
     // islands -1 (default): per-island solves where they change the answer measurably -- fp64 batches (held to the CPU
     // reference) and CG at any precision (CG stops at a looser point: joint vs per-island answers 4.9e-6 apart); fp32
     // Newton solves jointly (8e-15 apart, and a solve per island on one wave saves nothing)
-    if (L.d.island && (o.islands < 0 ? (sizeof(T) == 8 || L.d.cg) : o.islands != 0) && !(o.disableflags & DMC_DSBL_ISLAND) && solve_islands(nefc, &iter)) constraint_force_to_joint(nefc);
+    if (islands_on() && solve_islands(nefc, &iter)) constraint_force_to_joint(nefc);
     else {
       iter = primal_solve(nefc, evaluated, cc, gauss, changed);
       // (qfrc_constraint = J' efc_force is already that of the solution: every exit of primal_solve is preceded by a
@@ -5379,6 +5383,15 @@ struct StepCore {
 #define DMC_EPS_IMP 1      // (see primal_solve)
 #endif
   static constexpr int kNewtonRows = 16;      // rows per environment the register solve takes (one lane each, first 16-lane row)
+  // The register section takes the whole acceleration stage of such an environment (acc_regs): qfrc_smooth, qacc_smooth,
+  // the warm start's choice, the Newton solve and -- when mj_Euler's damped solve follows -- that solve too, on the rows of M
+  // it already holds.  -DDMC_NO_ACC_REGS: the register section is primal_solve's alone, the rest goes through LDS.
+#if !defined(DMC_NO_ACC_REGS)
+  static constexpr bool kAccRegs = kNewtonRegs;
+#else
+  static constexpr bool kAccRegs = false;
+#endif
+  static constexpr int kMiscEulerSolved = 2;      // `misc` slot: nonzero = sv_Mgrad holds mj_Euler's damped solve of this pass (set by acc_regs, consumed by euler_state)
 #ifndef DMC_HOST_EMU
   // fp32 is compiled with contraction on, and which of the LDS path's products end up fused into their sum is decided by
   // the vectoriser, not by the source: dot_n's products are paired off its vector loads into v_pk_mul_f32 and ADDED (no
@@ -5468,11 +5481,44 @@ struct StepCore {
       ch |= act != a; act = a;
     }
     cost = group_sum<LPE>(cost);
-    *changed = group_max<LPE>(ch);
+    if (changed) *changed = group_max<LPE>(ch);
     return cost;
   }
-  template <int N>
-  DMC_DEV int primal_solve_regs(int nefc, bool evaluated, T cc, T gauss, int changed) {
+  // factor_dense_rows' elimination of M + diag(dt d) on the register copy of M's rows, leaving what nr_factor leaves.
+  // (fp32: factor_dense_rows' diagonal is vectorised in pairs -- one rounded product dt d, packed adds -- and the entry an
+  // odd N leaves over is fused: seen in the ISA of every small model's mj_Euler, said here as nr_dot says its own)
+  template <int N> DMC_DEV void nr_factor_diag(const T (&M)[N], T dt, T d, T (&row)[N], T (&col)[N], T& dinv) const {
+#pragma clang fp contract(off)
+    const bool own = lane < N;
+    const T dv = dt*d;
+    T a[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+      T v = M[j] + dv;
+      if constexpr (sizeof(T) == 4) { if (j == N - 1 && (N & 1)) v = __builtin_fmaf(dt, d, M[j]); }
+      a[j] = (j == lane) ? v : M[j]; col[j] = 0;
+    }
+    dinv = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+      T akk = bcast_rows<LPE, N>(a[k], k);
+      if (akk < (T)DMC_MINVAL) akk = (T)DMC_MINVAL;
+      const T inv = t_rsqrt(akk);
+      const T lik = a[k] * inv;
+#pragma unroll
+      for (int j = k + 1; j < N; j++) {
+        const T ljk = bcast_rows<LPE, N>(lik, j);
+        a[j] = nmsub<true>(a[j], lik, ljk);
+        col[j] = lane == k ? ljk : col[j];
+      }
+      row[k] = (own && k < lane) ? lik : (T)0;
+      dinv = lane == k ? inv : dinv;
+    }
+  }
+  // ACC: the whole acceleration stage (fwd_acceleration + fwd_constraint) of the environment, nefc == 0 included, and
+  // with euler_next mj_Euler's damped solve; else primal_solve alone, from the point fwd_constraint left in LDS
+  template <int N, bool ACC = false>
+  DMC_DEV int primal_solve_regs(int nefc, bool evaluated, T cc, T gauss, int changed, bool euler_next = false) {
     const bool own = lane < N, rown = lane < nefc;
     const int i = own ? lane : 0, rl = rown ? lane : 0;
     const T scale = 1 / (o.meaninertia * (T)(N > 1 ? N : 1));
@@ -5496,10 +5542,30 @@ struct StepCore {
       const int t = r & ~3, rr = r < nefc ? r : (t < nefc ? t : 0);
       Jc[r] = S(efc_Jd)[rr*N + i];
     }
-    T qacc = S(qacc)[i];
-    const T qas = S(qacc_smooth)[i], qfs = S(qfrc_smooth)[i];
-    const T D_ = S(efc_D)[rl], aref_ = S(efc_aref)[rl], Ma_ = S(sv_Ma)[i], jar_ = S(efc_jar)[rl], force_ = S(efc_force)[rl];
-    const int act_ = SI(efc_active)[rl];
+    T qacc, qas, qfs, Ma_ = 0, jar_ = 0, force_ = 0;
+    int act_ = 0;
+    const T D_ = S(efc_D)[rl], aref_ = S(efc_aref)[rl];
+    if constexpr (ACC) {
+      // fwd_acceleration: qfrc_smooth, and qacc_smooth by chol_solve_rows' loads and sweeps on the factor of M
+      const DMC_LDS T* Lm = (const DMC_LDS T*)M_factor();
+      const int ci = tri_c0(i, N);
+      T mrow[N], mcol[N];
+#pragma unroll
+      for (int k = 0; k < N; k++) {
+        const T r_ = Lm[tri_c0(k, N) + ((own && k < i) ? i - k : 0)], c_ = Lm[ci + ((own && k > i) ? k - i : 0)];
+        mrow[k] = (own && k < i) ? r_ : (T)0; mcol[k] = (own && k > i) ? c_ : (T)0;
+      }
+      const T mdinv_ = Lm[ci];
+      const T fp = S(qfrc_passive)[i], fb = S(qfrc_bias)[i], fa = S(qfrc_applied)[i], fu = S(qfrc_actuator)[i];
+      qacc = S(qacc_warmstart)[i];
+      qfs = fp - fb + fa + fu;
+      qas = nr_solve<N>(mrow, mcol, own ? mdinv_ : (T)0, qfs);
+      if (own) { S(qfrc_smooth)[lane] = qfs; S(qacc_smooth)[lane] = qas; }
+      DMC_PROF(PROF_ACC);
+    } else {
+      qacc = S(qacc)[i]; qas = S(qacc_smooth)[i]; qfs = S(qfrc_smooth)[i];
+      Ma_ = S(sv_Ma)[i]; jar_ = S(efc_jar)[rl]; force_ = S(efc_force)[rl]; act_ = SI(efc_active)[rl];
+    }
     const T D = rown ? D_ : (T)0;
     T Ma, jar, force = 0;
     int act;
@@ -5508,7 +5574,7 @@ struct StepCore {
       if (own) g += (Ma - qfs) * (qacc - qas);
       return (T)0.5 * group_sum<LPE>(g);
     };
-    if (!evaluated) {
+    auto evaluate = [&]() __attribute__((always_inline)) {
       Ma = nr_dot<N>(M, qacc);
       const T ja = nr_dot<N>(Jr, qacc) - aref_;
       jar = rown ? ja : (T)0;
@@ -5516,10 +5582,27 @@ struct StepCore {
       act = -1;      // no factor of H yet
       cc = nr_update(rown, jar, D, force, act, &changed);
       gauss = gauss_cost_regs();
-    } else { Ma = Ma_; jar = rown ? jar_ : (T)0; force = rown ? force_ : (T)0; act = act_; }
+    };
+    T fc = 0, grad = 0, Mgrad = 0;
+    int iter = 0;
+    if constexpr (ACC) {
+      // fwd_constraint's warm start: qacc_warmstart stays unless its cost is above qacc_smooth's (whose Gauss term is zero)
+      if (nefc == 0) qacc = qas;
+      else if (!(o.disableflags & DMC_DSBL_WARMSTART)) {
+        const T js = nr_dot<N>(Jr, qas) - aref_;
+        T f0 = 0;
+        int a0 = 0;
+        const T cs = nr_update(rown, rown ? js : (T)0, D, f0, a0, nullptr);
+        evaluate();
+        if (cc + gauss > cs) { qacc = qas; evaluate(); }
+      } else { qacc = qas; evaluate(); }
+    } else {
+      if (!evaluated) evaluate();
+      else { Ma = Ma_; jar = rown ? jar_ : (T)0; force = rown ? force_ : (T)0; act = act_; }
+    }
+    const bool solve = !ACC || nefc > 0;      // (ACC without a row: qacc_smooth is the answer, no factor, no iteration)
     T cost = cc + gauss;
     DMC_PROF(PROF_SOL_INIT);
-    T fc, grad, Mgrad;
     auto gradient_regs = [&](int refactor) __attribute__((always_inline)) {
       fc = nr_jtf(Jc, force, nefc);
       grad = Ma - qfs - fc;
@@ -5532,12 +5615,11 @@ struct StepCore {
       Mgrad = nr_solve<N>(row, col, dinv, grad);
       DMC_PROF(PROF_SOLVE);
     };
-    gradient_regs(1);
+    if (solve) gradient_regs(1);
     T search = -Mgrad;
     DMC_PROF(PROF_SOL_GRAD);
-    int iter = 0;
     const bool anch = anchored();
-    while (iter < o.iterations) {
+    while (solve && iter < o.iterations) {
       if (iter == DMC_PRIO_ITER) __builtin_amdgcn_s_setprio(2);      // (see primal_solve)
       T lscost = 0;
       DMC_TSUB(3, iter == 0, 4);
@@ -5586,13 +5668,37 @@ struct StepCore {
       if (improvement < tol_imp || gradient < tol_grad) break;
     }
     __builtin_amdgcn_s_setprio(0);
+    if constexpr (ACC) {
+      // mj_Euler's damped solve (euler_state): (M + dt damping)^-1 (qfrc_smooth + qfrc_constraint)
+      if (euler_next) {
+        // (factored here, after the loop: beside the qacc_smooth substitution its row and column stay live across the
+        // loop, 20 - 22 VGPRs on kernels that sit near the cap)
+        T erow[N], ecol[N], edinv;
+        if constexpr (!keep) load_M();
+        nr_factor_diag<N>(M, o.timestep, MR(dof_damping)[i], erow, ecol, edinv);
+        const T qe = nr_solve<N>(erow, ecol, edinv, qfs + fc);
+        if (own) S(sv_Mgrad)[lane] = qe;
+        if (lane == 0) S(misc)[kMiscEulerSolved] = (T)1;
+      }
+      if (own) S(qacc_warmstart)[lane] = qacc;
+      if (lane == 0) SI(imisc)[IM_ITER] = iter;
+    }
     // the one exit: what the rest of the step reads
     if (own) { S(qacc)[lane] = qacc; S(qfrc_constraint)[lane] = fc; }
     if (rown) { S(efc_force)[lane] = force; S(efc_jar)[lane] = jar; SI(efc_active)[lane] = act; }
     DMC_WSYNC();
     return iter;
   }
+  // the environments whose whole acceleration stage runs in registers: those whose Newton solve does (primal_solve), with
+  // the paths of fwd_acceleration / fwd_constraint that the register section does not restate left out
+  DMC_DEV bool acc_regs_ok(int nefc) const {
+    return L.d.jfull && !L.d.msparse && !L.d.elliptic && !L.d.cg && !L.d.nslip && !general_rows() && nefc <= kNewtonRows
+           && !L.d.pgs && !o.xfrc && !islands_on();
+  }
 #endif
+  DMC_DEV bool islands_on() const {
+    return L.d.island && (o.islands < 0 ? (sizeof(T) == 8 || L.d.cg) : o.islands != 0) && !(o.disableflags & DMC_DSBL_ISLAND);
+  }
   DMC_DEV int primal_solve(int nefc, bool evaluated, T cc, T gauss, int changed) {
 #ifndef DMC_HOST_EMU
     if constexpr (kNewtonRegs) {
@@ -5869,10 +5975,14 @@ struct StepCore {
       }
     }
     if (implicitfast || (o.any_damping && !(o.disableflags & (DMC_DSBL_EULERDAMP | DMC_DSBL_DAMPER)))) {
-      FOR_LANES(i, nv) S(sv_grad)[i] = S(qfrc_smooth)[i] + S(qfrc_constraint)[i];
-      DMC_WSYNC();
-      factor_M(true, implicitfast ? S(sv_search) : MR(dof_damping));
-      chol_solve(S(sv_Mgrad), S(qLH), S(sv_grad), nv, true);
+      bool solved = false;      // the acceleration stage's register section left the solve in sv_Mgrad (the mark is cleared here, where it is consumed)
+      if constexpr (kAccRegs) { solved = S(misc)[kMiscEulerSolved] != 0; if (lane == 0) S(misc)[kMiscEulerSolved] = 0; }
+      if (!solved) {
+        FOR_LANES(i, nv) S(sv_grad)[i] = S(qfrc_smooth)[i] + S(qfrc_constraint)[i];
+        DMC_WSYNC();
+        factor_M(true, implicitfast ? S(sv_search) : MR(dof_damping));
+        chol_solve(S(sv_Mgrad), S(qLH), S(sv_grad), nv, true);
+      }
       qacc = S(sv_Mgrad);
     }
     FOR_LANES(i, nv) S(qvel)[i] += dt*qacc[i];
@@ -5947,6 +6057,7 @@ struct StepCore {
     FOR_LANES(i, L.d.nv) { S(qvel)[i] = 0; S(qacc_warmstart)[i] = 0; S(qfrc_applied)[i] = 0; }
     FOR_LANES(i, L.d.nu) S(ctrl)[i] = 0;
     if (L.d.na) FOR_LANES(i, L.d.na) { S(act)[i] = 0; S(act_dot)[i] = 0; }
+    if constexpr (kAccRegs) { if (lane == 0) S(misc)[kMiscEulerSolved] = 0; }      // (mj_checkAcc's retry: the solve left for mj_Euler is the discarded pass's)
     time_ = 0;
     DMC_WSYNC();
   }
@@ -5983,8 +6094,24 @@ struct StepCore {
     DMC_PROF(PROF_SENS);
   }
   // Acceleration stage (mj_step2 without the integrator)
-  DMC_DEV void stage_acc(bool disable_actuation, bool skipsensor) {
-    fwd_actuation(disable_actuation); DMC_PROF(PROF_ACT); fwd_acceleration(); DMC_PROF(PROF_ACC); fwd_constraint();
+  // euler_next: the caller integrates this pass with call_euler() next (not an RK4 stage, not mj_forward)
+  DMC_DEV void stage_acc(bool disable_actuation, bool skipsensor, bool euler_next = false) {
+    fwd_actuation(disable_actuation); DMC_PROF(PROF_ACT);
+    bool regs = false;
+#ifndef DMC_HOST_EMU
+    if constexpr (kAccRegs) {
+      // (per environment: the two environments of a wave may take different paths)
+      const int nefc = SI(imisc)[IM_NEFC];
+      if (lane == 0) S(misc)[kMiscEulerSolved] = 0;
+      regs = acc_regs_ok(nefc);
+      if (regs) {
+        const bool damped = euler_next && o.any_damping && !(o.disableflags & (DMC_DSBL_EULERDAMP | DMC_DSBL_DAMPER))
+                            && !(kFeat && o.integrator == DMC_INT_IMPLICITFAST);
+        primal_solve_regs<LS::kNV, true>(nefc, false, 0, 0, 1, damped);
+      }
+    }
+#endif
+    if (!regs) { fwd_acceleration(); DMC_PROF(PROF_ACC); fwd_constraint(); }
     DMC_PROF(PROF_X8);      // (what fwd_constraint does after the solver's last marker: forces at the solution, J' f)
     if (!skipsensor) sensors_acc();
     DMC_PROF(PROF_SENS);
@@ -6033,9 +6160,11 @@ struct StepCore {
     StageFns<T, LPE, LS>::posvel(ls, (const DMC_LDS StepOpts<T>*)&o, (DMC_LDS int*)mi, (DMC_LDS T*)mr, gc, (DMC_LDS T*)s,
                                  (DMC_LDS int*)si, lane, (partial ? 1 : 0) | (skipsensor ? 2 : 0) | (havekin ? 4 : 0), outmask);
   }
-  DMC_DEV void call_acc(bool disable_actuation, bool skipsensor) {
+  DMC_DEV void call_acc(bool disable_actuation, bool skipsensor, bool euler_next = false) {
+    int flags = (disable_actuation ? 1 : 0) | (skipsensor ? 2 : 0);
+    if constexpr (kAccRegs) flags |= euler_next ? 4 : 0;      // (only where it is read: the other kernels' code stays as it was)
     StageFns<T, LPE, LS>::acc(ls, (const DMC_LDS StepOpts<T>*)&o, (DMC_LDS int*)mi, (DMC_LDS T*)mr, gc, (DMC_LDS T*)s,
-                              (DMC_LDS int*)si, lane, (disable_actuation ? 1 : 0) | (skipsensor ? 2 : 0));
+                              (DMC_LDS int*)si, lane, flags);
   }
   DMC_DEV void call_euler() {
     StageFns<T, LPE, LS>::euler(ls, (const DMC_LDS StepOpts<T>*)&o, (DMC_LDS int*)mi, (DMC_LDS T*)mr, gc, (DMC_LDS T*)s,
@@ -6044,7 +6173,7 @@ struct StepCore {
   }
 #else
   DMC_DEV void call_posvel(bool partial, int outmask, bool skipsensor, bool havekin = false) { stage_posvel(partial, outmask, skipsensor, havekin); }
-  DMC_DEV void call_acc(bool disable_actuation, bool skipsensor) { stage_acc(disable_actuation, skipsensor); }
+  DMC_DEV void call_acc(bool disable_actuation, bool skipsensor, bool euler_next = false) { stage_acc(disable_actuation, skipsensor, euler_next); }
   DMC_DEV void call_euler() { euler(); }
 #endif
   DMC_DEV void load_ctrl_seq(const StepIO<T>& io, int env, int t) {
@@ -6091,7 +6220,7 @@ struct StepCore {
     int retried = 0;
     for (;;) {
       if (!have || retried) call_posvel(false, outmask, true);
-      call_acc(false, false);
+      call_acc(false, false, true);
       if (!retried && bad_acc()) {
         if (lane == 0) SI(imisc)[IM_WARN + DMC_WARN_BADQACC]++;     // mj_checkAcc: reset + forward
         if (!(o.disableflags & DMC_DSBL_AUTORESET)) { DMC_WSYNC(); reset_state(); retried = 1; continue; }
@@ -6192,7 +6321,7 @@ struct StepCore {
         if (mode == 3 && stage == 0 && it > 0 && it % nsub == 0) store_seq(io, env, it / nsub - 1);
         if (mode == 0 && stage == 0 && it >= 1) probe_store(io, env, it - 1, 1);      // the state after `it` physics steps
         if (trailing && !fwd_after) break;
-        call_acc(mode == 2, stage > 0 || !sens_acc);      // (the ONE call site of the acceleration stage)
+        call_acc(mode == 2, stage > 0 || !sens_acc, stepping && !trailing && nstage == 1);      // (the ONE call site of the acceleration stage)
         if (trailing) break;      // legacy_step 2: the launch ends with mj_forward's acceleration stage at the new state
         if (it == 0 && stage == 0) trace_stamp(io, env, 5);
         if (stage == 0 && stepping && !retried && bad_acc()) {
@@ -6244,7 +6373,7 @@ struct StageFns {
   static DMC_FN void acc(LS ls, const DMC_LDS StepOpts<T>* o, DMC_LDS int* mi, DMC_LDS T* mr, const int* gc, DMC_LDS T* s,
                          DMC_LDS int* si, int lane, int flags) {
     Core c(ls, *(const StepOpts<T>*)o, (const int*)mi, (const T*)mr, gc, (T*)s, (int*)si, lane);
-    c.stage_acc(flags & 1, flags & 2);
+    c.stage_acc(flags & 1, flags & 2, flags & 4);
   }
   static DMC_FN void ns_build(LS ls, const DMC_LDS StepOpts<T>* o, DMC_LDS int* mi, DMC_LDS T* mr, const int* gc, DMC_LDS T* s,
                               DMC_LDS int* si, int lane, int nf) {
