@@ -966,6 +966,20 @@ struct StepCore {
 #endif
     return L.d.jglobal >= 2 ? (const T*)o.g_mr : mr;
   }
+  // Content facts of the model (StepDims::jtypes, nsens_*): constants in a model-specialised kernel, whose code for what
+  // the model does not contain goes away.  -DDMC_NO_CONTENT_DIMS: everything may occur (the reference build of
+  // tests/test_content_dims_cpu.py and tests/test_gpu_fixed_stages.py).
+#ifndef DMC_NO_CONTENT_DIMS
+  DMC_DEV bool has_jnt(int type) const { return (L.d.jtypes >> type) & 1; }
+  DMC_DEV int nsens(int stage) const { return stage == DMC_STAGE_POS ? L.d.nsens_pos : (stage == DMC_STAGE_VEL ? L.d.nsens_vel : L.d.nsens_acc); }
+  DMC_DEV int nsens_rne() const { return L.d.nsens_rne; }
+  DMC_DEV int nsens_touch() const { return L.d.nsens_touch; }
+#else
+  DMC_DEV bool has_jnt(int) const { return true; }
+  DMC_DEV int nsens(int) const { return L.d.nsensor; }
+  DMC_DEV int nsens_rne() const { return L.d.nsensor; }
+  DMC_DEV int nsens_touch() const { return L.d.nsensor; }
+#endif
   // Opaque copy of an env index: stops the compiler from forming HBM addresses long before
   // they are used and carrying them across the out-of-line stage calls (callee-saved VGPRs,
   // spilled to scratch once there are too many).
@@ -1322,7 +1336,7 @@ struct StepCore {
   DMC_DEV void body_local_pose(int i) {
     T p[3], q[4];
     const int jntadr = MI(body_jntadr)[i], jntnum = MI(body_jntnum)[i];
-    if (jntnum == 1 && MI(jnt_type)[jntadr] == DMC_JNT_FREE) {
+    if (has_jnt(DMC_JNT_FREE) && jntnum == 1 && MI(jnt_type)[jntadr] == DMC_JNT_FREE) {
       const int qa = MI(jnt_qposadr)[jntadr];
       for (int k = 0; k < 3; k++) p[k] = S(qpos)[qa + k];
       for (int k = 0; k < 4; k++) q[k] = S(qpos)[qa + 3 + k];
@@ -1347,12 +1361,12 @@ struct StepCore {
         mul_mat_vec3(anchor, R, MR(jnt_pos) + 3*j);
         anchor[0] += p[0]; anchor[1] += p[1]; anchor[2] += p[2];
         for (int k = 0; k < 3; k++) { S(xanchor)[3*j + k] = anchor[k]; S(xaxis)[3*j + k] = axis[k]; }
-        if (t == DMC_JNT_SLIDE) {
+        if (has_jnt(DMC_JNT_SLIDE) && t == DMC_JNT_SLIDE) {
           const T d = S(qpos)[qa] - MR(qpos0)[qa];
           p[0] += axis[0]*d; p[1] += axis[1]*d; p[2] += axis[2]*d;
-        } else if (t == DMC_JNT_BALL || t == DMC_JNT_HINGE) {
+        } else if ((has_jnt(DMC_JNT_BALL) && t == DMC_JNT_BALL) || (has_jnt(DMC_JNT_HINGE) && t == DMC_JNT_HINGE)) {
           T qloc[4], vec[3];
-          if (t == DMC_JNT_BALL) { for (int k = 0; k < 4; k++) qloc[k] = S(qpos)[qa + k]; normalize4(qloc); }
+          if (has_jnt(DMC_JNT_BALL) && t == DMC_JNT_BALL) { for (int k = 0; k < 4; k++) qloc[k] = S(qpos)[qa + k]; normalize4(qloc); }
           else axisangle2quat(qloc, MR(jnt_axis) + 3*j, S(qpos)[qa] - MR(qpos0)[qa]);
           mul_quat(q, q, qloc);
           rot_vec_quat(vec, MR(jnt_pos) + 3*j, q);
@@ -3254,12 +3268,14 @@ struct StepCore {
   DMC_DEV void sensors_acc() {
     if ((o.disableflags & DMC_DSBL_SENSOR) || L.d.nsensor == 0) return;
     int need = 0;
+    if (nsens_rne())
     for (int i = 0; i < L.d.nsensor; i++) {
       const int t = MI(sensor_type)[i];
       if (MI(sensor_stage)[i] == DMC_STAGE_ACC && (t == DMC_SENS_ACCELEROMETER || t == DMC_SENS_FORCE || t == DMC_SENS_TORQUE)) need = 1;
     }
     if (need) rne_post_constraint();
     const int ncon = SI(imisc)[IM_NCON];
+    if (nsens(DMC_STAGE_ACC))
     FOR_LANES(i, L.d.nsensor) {
       if (MI(sensor_stage)[i] != DMC_STAGE_ACC) continue;
       T* out = S(sensordata) + MI(sensor_adr)[i];
@@ -3272,7 +3288,7 @@ struct StepCore {
       mul_quat(q, SG(xquat) + 4*body, MRS(site_quat) + 4*id);
       quat2mat(smat, q);
       const T* rc = S(subtree_com) + 3*MI(body_rootid)[body];
-      if (t == DMC_SENS_TOUCH) {
+      if (nsens_touch() && t == DMC_SENS_TOUCH) {
         T tot = 0;
         for (int c = 0; c < ncon; c++) {
           if (SI(con_efc)[c] < 0) continue;
@@ -3287,7 +3303,7 @@ struct StepCore {
           if (ray_geom(spos, smat, MRS(site_size) + 3*id, S(con_pos) + 3*c, ray, MI(site_type)[id]) >= 0) tot += lf[0];
         }
         out[0] = tot;
-      } else if (t == DMC_SENS_ACCELEROMETER) {
+      } else if (nsens_rne() && t == DMC_SENS_ACCELEROMETER) {
         T dif[3] = {spos[0] - rc[0], spos[1] - rc[1], spos[2] - rc[2]}, tmp[3], lin[3], cor[3], tmp2[3], vlin[3];
         const T* ca = S(cacc) + 6*body; const T* cv = S(cvel) + 6*body;
         cross3(tmp, dif, ca);
@@ -3297,9 +3313,9 @@ struct StepCore {
         cross3(cor, cv, vlin);
         for (int k = 0; k < 3; k++) lin[k] += cor[k];
         mul_matT_vec3(out, smat, lin);
-      } else if (t == DMC_SENS_FORCE) {
+      } else if (nsens_rne() && t == DMC_SENS_FORCE) {
         mul_matT_vec3(out, smat, S(cfrc) + 6*body + 3);
-      } else if (t == DMC_SENS_TORQUE) {
+      } else if (nsens_rne() && t == DMC_SENS_TORQUE) {
         T dif[3] = {spos[0] - rc[0], spos[1] - rc[1], spos[2] - rc[2]}, tmp[3], tq[3];
         cross3(tmp, dif, S(cfrc) + 6*body + 3);
         for (int k = 0; k < 3; k++) tq[k] = S(cfrc)[6*body + k] - tmp[k];
@@ -3329,6 +3345,7 @@ struct StepCore {
   DMC_DEV void sensors(int stage) {
     if ((o.disableflags & DMC_DSBL_SENSOR) || L.d.nsensor == 0) return;
     if (L.d.nstv && stage == DMC_STAGE_VEL) subtree_linvel_sensors();
+    if (nsens(stage))      // (a model whose only sensors are subtreelinvel ones has nothing left for the loop)
     FOR_LANES(i, L.d.nsensor) {
       if (MI(sensor_stage)[i] != stage) continue;
       T* out = S(sensordata) + MI(sensor_adr)[i];
@@ -4305,6 +4322,18 @@ struct StepCore {
   // contact's other rows carry nothing.  An evaluation of the soccer / 62-dof models was a chain of LDS look-ups (row
   // type -> contact -> first row -> nine aggregates) per row before the arithmetic started: 22 % / 14 % of their step.
   enum { LSK_NONE = 0, LSK_EQUALITY, LSK_FRICTION, LSK_ONESIDED, LSK_CONE };
+  // Lanes the reductions of the register section (primal_solve_regs, primal_search<true>) run over.  Every dof and every
+  // row of that section sits in the FIRST 16-lane row of its group and the lanes of the group's other rows contribute
+  // zeros, so the four DPP steps inside the row already leave the group's sum in the first row; the row swap and the add
+  // that follow in group_sum<32> (two dependent instructions on the chain of ~25 reductions per Newton iteration) added
+  // an exact zero.  The bits are the same: each lane's term is `0 + products`, never -0, so neither is the row's sum, and
+  // x + (+0) = x for every other x.  The other rows receive their own row's sum, zero: primal_solve_regs keeps them out of
+  // the factorisation and the iterations (they hold nothing and store nothing).  -DDMC_NO_ROW_REDUCE: all LPE lanes.
+#if !defined(DMC_NO_ROW_REDUCE)
+  static constexpr int kRegsRed = LPE < 16 ? LPE : 16;
+#else
+  static constexpr int kRegsRed = LPE;
+#endif
   struct LSRows { T jar, jv, D; bool on; bool gen; int kind; T f, rf, U0, V0, UU, UV, VV, mu, b0, b1, b2, Dm, NT0, T0; bool bottom0, middle0; };
   // (round 5: loads first and unpredicated, the contact block as six statically indexed rows -- see constraint_update_ell)
   DMC_DEV void ls_load_gen(LSRows& g, int nefc) {
@@ -4432,6 +4461,7 @@ struct StepCore {
     p->d1 = 2*q2 + cd1;
     if (p->d1 <= 0) p->d1 = (T)DMC_MINVAL;
   }
+  template <int RED = LPE>      // (RED: lanes of the reductions over register-resident rows -- kRegsRed from primal_search<true>)
   DMC_DEV void ls_eval(LSPoint* p, const T* qg, int nefc, int* evals, const LSRows& rw) {
 #ifdef DMC_HOST_EMU
     emu_ls_counts()[1]++;
@@ -4451,7 +4481,7 @@ struct StepCore {
         const T D = rw.D, dj0 = D*jar;
         q0 += (T)0.5*jar*dj0; q1 += jv*dj0; q2 += (T)0.5*D*jv*jv;
       }
-      q0 = group_sum<LPE>(q0) + (ls_relative<T>() ? (T)0 : qg[0]); q1 = group_sum<LPE>(q1) + qg[1]; q2 = group_sum<LPE>(q2) + qg[2];
+      q0 = group_sum<RED>(q0) + (ls_relative<T>() ? (T)0 : qg[0]); q1 = group_sum<RED>(q1) + qg[1]; q2 = group_sum<RED>(q2) + qg[2];
       p->cost = a*a*q2 + a*q1 + q0;
       p->d0 = 2*a*q2 + q1;
       p->d1 = 2*q2;
@@ -4464,13 +4494,14 @@ struct StepCore {
     p->alpha = rv[0]; p->cost = rv[1]; p->d0 = rv[2]; p->d1 = rv[3];
     (*evals)++;
   }
+  template <int RED = LPE>
   DMC_DEV int ls_update_bracket(LSPoint* p, const LSPoint* cand, LSPoint* pnext, const T* qg, int nefc, int* evals, const LSRows& rw) {
     int flag = 0;
     for (int i = 0; i < 3; i++) {
       if (p->d0 < 0 && cand[i].d0 < 0 && p->d0 < cand[i].d0) { *p = cand[i]; flag = 1; }
       else if (p->d0 > 0 && cand[i].d0 > 0 && p->d0 > cand[i].d0) { *p = cand[i]; flag = 2; }
     }
-    if (flag) { pnext->alpha = p->alpha - p->d0/p->d1; ls_eval(pnext, qg, nefc, evals, rw); }
+    if (flag) { pnext->alpha = p->alpha - p->d0/p->d1; ls_eval<RED>(pnext, qg, nefc, evals, rw); }
     return flag;
   }
   // REGS (primal_solve_regs): M v and J v are the caller's, in registers -- `pre` brings the lane's terms of the four dof
@@ -4479,6 +4510,7 @@ struct StepCore {
   template <bool REGS = false>
   DMC_DEV T primal_search(int nefc, T gauss, T scale, T* lscost, const LSPre& pre = LSPre()) {
     *lscost = 0;      // cost of the returned point (relative to alpha = 0 in fp32: minus the iteration's improvement)
+    constexpr int RED = REGS ? kRegsRed : LPE;
 #ifdef DMC_HOST_EMU
     emu_ls_counts()[0]++;
 #endif
@@ -4501,7 +4533,7 @@ struct StepCore {
       else { a1 += sr*S(sv_Ma)[i]; a2 += S(qfrc_smooth)[i]*sr; }
       a3 += sr*S(sv_Mv)[i]; a4 += sr*sr;
     }
-    a1 = group_sum<LPE>(a1); if (!anch) a2 = group_sum<LPE>(a2); a3 = group_sum<LPE>(a3); a4 = group_sum<LPE>(a4);
+    a1 = group_sum<RED>(a1); if (!anch) a2 = group_sum<RED>(a2); a3 = group_sum<RED>(a3); a4 = group_sum<RED>(a4);
     T qg[3] = {gauss, a1 - a2, (T)0.5*a3};
     const T snorm = t_sqrt(a4);
     if (snorm < (T)DMC_MINVAL) return 0;
@@ -4517,7 +4549,7 @@ struct StepCore {
 #endif
     DMC_PROF(PROF_LS_SETUP);
     LSPoint p0, p1, p2, pmid, p1next, p2next;
-    p0.alpha = 0; ls_eval(&p0, qg, nefc, &evals, rw);
+    p0.alpha = 0; ls_eval<RED>(&p0, qg, nefc, &evals, rw);
     // fp32: the slope cannot be resolved below a few ulp of the slope at alpha = 0 (the sums that form it are that
     // large), while MuJoCo's gtol = tolerance * ls_tolerance * |search| / scale sits ~1e-10 below it: fp64 gets there in
     // 4.5 evaluations per search (quadratic convergence), fp32 never did and refined the bracket until no candidate
@@ -4530,7 +4562,7 @@ struct StepCore {
 #else
     if (sizeof(T) == 4) gtol = t_max(gtol, (T)(DMC_LS_SLOPE_ULPS * 1.1920929e-7) * t_abs(p0.d0));
 #endif
-    p1.alpha = p0.alpha - p0.d0/p0.d1; ls_eval(&p1, qg, nefc, &evals, rw);
+    p1.alpha = p0.alpha - p0.d0/p0.d1; ls_eval<RED>(&p1, qg, nefc, &evals, rw);
 #ifdef DMC_HOST_EMU
     if (getenv("DMC_EMU_TRACE_LS")) fprintf(stderr, "    ls: p0 cost %.6e d0 %.6e d1 %.6e | p1 alpha %.9e cost %.6e d0 %.6e d1 %.6e | gtol %.3e qg1 %.6e\n",
                                            (double)p0.cost, (double)p0.d0, (double)p0.d1, (double)p1.alpha, (double)p1.cost, (double)p1.d0, (double)p1.d1, (double)gtol, (double)qg[1]);
@@ -4542,23 +4574,23 @@ struct StepCore {
     p2 = p1;
     while (p1.d0*dir <= -gtol && evals < lsmax) {
       p2 = p1; p2update = 1;
-      p1.alpha -= p1.d0/p1.d1; ls_eval(&p1, qg, nefc, &evals, rw);
+      p1.alpha -= p1.d0/p1.d1; ls_eval<RED>(&p1, qg, nefc, &evals, rw);
       if (t_abs(p1.d0) < gtol) { *lscost = p1.cost; return p1.alpha; }
     }
     if (evals >= lsmax) { *lscost = p1.cost; return p1.alpha; }
     if (!p2update) { *lscost = p1.cost; return p1.alpha; }
     p2next = p1;
-    p1next.alpha = p1.alpha - p1.d0/p1.d1; ls_eval(&p1next, qg, nefc, &evals, rw);
+    p1next.alpha = p1.alpha - p1.d0/p1.d1; ls_eval<RED>(&p1next, qg, nefc, &evals, rw);
     while (evals < lsmax) {
-      pmid.alpha = (T)0.5*(p1.alpha + p2.alpha); ls_eval(&pmid, qg, nefc, &evals, rw);
+      pmid.alpha = (T)0.5*(p1.alpha + p2.alpha); ls_eval<RED>(&pmid, qg, nefc, &evals, rw);
       LSPoint cand[3] = {p1next, p2next, pmid};
       bool found = false; T best_cost = 0, best_alpha = 0;   // first candidate of lowest cost (no dynamic indexing)
       for (int i = 0; i < 3; i++) if (t_abs(cand[i].d0) < gtol && (!found || cand[i].cost < best_cost)) {
         found = true; best_cost = cand[i].cost; best_alpha = cand[i].alpha;
       }
       if (found) { *lscost = best_cost; return best_alpha; }
-      const int b1 = ls_update_bracket(&p1, cand, &p1next, qg, nefc, &evals, rw);
-      const int b2 = ls_update_bracket(&p2, cand, &p2next, qg, nefc, &evals, rw);
+      const int b1 = ls_update_bracket<RED>(&p1, cand, &p1next, qg, nefc, &evals, rw);
+      const int b2 = ls_update_bracket<RED>(&p2, cand, &p2next, qg, nefc, &evals, rw);
       if (!b1 && !b2) { if (pmid.cost < p0.cost) { *lscost = pmid.cost; return pmid.alpha; } return 0; }
     }
     if (p1.cost <= p2.cost && p1.cost < p0.cost) { *lscost = p1.cost; return p1.alpha; }
@@ -5480,8 +5512,8 @@ struct StepCore {
       if (sizeof(T) == 4) cost += a ? (T)0.5*dj*jar : (T)0; else if (a) cost += (T)0.5*D*jar*jar;
       ch |= act != a; act = a;
     }
-    cost = group_sum<LPE>(cost);
-    if (changed) *changed = group_max<LPE>(ch);
+    cost = group_sum<kRegsRed>(cost);
+    if (changed) *changed = group_max<kRegsRed>(ch);
     return cost;
   }
   // factor_dense_rows' elimination of M + diag(dt d) on the register copy of M's rows, leaving what nr_factor leaves.
@@ -5572,7 +5604,7 @@ struct StepCore {
     auto gauss_cost_regs = [&]() __attribute__((always_inline)) {
       T g = 0;
       if (own) g += (Ma - qfs) * (qacc - qas);
-      return (T)0.5 * group_sum<LPE>(g);
+      return (T)0.5 * group_sum<kRegsRed>(g);
     };
     auto evaluate = [&]() __attribute__((always_inline)) {
       Ma = nr_dot<N>(M, qacc);
@@ -5600,7 +5632,9 @@ struct StepCore {
       if (!evaluated) evaluate();
       else { Ma = Ma_; jar = rown ? jar_ : (T)0; force = rown ? force_ : (T)0; act = act_; }
     }
-    const bool solve = !ACC || nefc > 0;      // (ACC without a row: qacc_smooth is the answer, no factor, no iteration)
+    // (ACC without a row: qacc_smooth is the answer, no factor, no iteration.  The lanes of the group's other rows, whose
+    // reductions are their own row's zeros (kRegsRed): neither -- they would leave the loop at its first test anyway)
+    const bool solve = (!ACC || nefc > 0) && (kRegsRed == LPE || lane < kRegsRed);
     T cost = cc + gauss;
     DMC_PROF(PROF_SOL_INIT);
     auto gradient_regs = [&](int refactor) __attribute__((always_inline)) {
@@ -5657,7 +5691,7 @@ struct StepCore {
       T g2 = 0, ma2 = 0;
       search = -Mgrad;
       if (own) { g2 += grad*grad; ma2 += Ma*Ma; }
-      g2 = group_sum<LPE>(g2); ma2 = group_sum<LPE>(ma2);
+      g2 = group_sum<kRegsRed>(g2); ma2 = group_sum<kRegsRed>(ma2);
       const T improvement = ls_relative<T>() ? -scale*lscost : scale*(oldcost - cost), gradient = scale*t_sqrt(g2);
       iter++;
       // primal_solve's termination tests

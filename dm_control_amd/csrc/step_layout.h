@@ -76,6 +76,19 @@ struct StepDims {
                  // The residency per CU of these models is bounded by LDS and their step is long enough that a few L2
                  // round trips do not show: level 1 took humanoid 6 -> 8 and the 62-dof models 2 -> 3 environments per
                  // CU, level 2 the 62-dof models to 4; on the 27 / 30-dof models level 2 gains no residency and costs 1-2 %.
+  // ---- content facts: what the model CONTAINS, so that a model-specialised kernel (where they are constants) drops the
+  // code of what it does not contain; the generic kernels read them at run time and behave as before.  Each one only
+  // says "may occur": the code it guards still tests every joint / sensor itself, so any superset gives the same result
+  // (-DDMC_NO_CONTENT_DIMS makes the kernel assume everything occurs: StepCore::has_jnt / nsens).  They are computed by
+  // step_tables_build from the model's INTEGER tables (jnt_type, sensor_type, sensor_needstage) alone, which nothing
+  // edits after batch creation -- dmc_batch_set_model_real reaches real tables only, dmc_batch_set_env_geoms no joint and
+  // no sensor -- and they are part of the layout dmc_batch_attach_specialised compares byte for byte.
+  int jtypes;      // bit t: a joint of type t (DMC_JNT_*) exists
+  int nsens_pos;   // sensors of the position stage that the loop of StepCore::sensors() evaluates (subtreelinvel sensors are not among them)
+  int nsens_vel;   // the same for the velocity stage
+  int nsens_acc;   // sensors of the acceleration stage
+  int nsens_rne;   // of those, accelerometer / force / torque: they need rne_post_constraint
+  int nsens_touch; // of those, touch sensors: contact forces and a ray test per contact
 };
 
 // Constraint Jacobian storage.  Rows come in MuJoCo's order (equality, dof friction, joint limit,

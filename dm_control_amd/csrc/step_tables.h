@@ -110,6 +110,18 @@ inline bool step_tables_build(StepTables* t, const HostModel& m, int nconmax, in
   d.nmocap = m.nmocap;
   for (int i = 0; i < m.nsensor; i++) if (m.sensor_type[i] == DMC_SENS_RANGEFINDER) d.nrf++;
   if (d.nstv && m.nbody > 64) { *err = "subtreelinvel sensors need nbody <= 64"; return false; }
+  // content facts (StepDims): from the integer tables only
+  for (int j = 0; j < m.njnt; j++) d.jtypes |= 1 << (m.jnt_type[j] & 31);
+  for (int i = 0; i < m.nsensor; i++) {
+    const int ty = m.sensor_type[i], st = m.sensor_needstage[i];
+    if (st == DMC_STAGE_POS && ty != DMC_SENS_SUBTREELINVEL) d.nsens_pos++;
+    if (st == DMC_STAGE_VEL && ty != DMC_SENS_SUBTREELINVEL) d.nsens_vel++;
+    if (st == DMC_STAGE_ACC) {
+      d.nsens_acc++;
+      if (ty == DMC_SENS_ACCELEROMETER || ty == DMC_SENS_FORCE || ty == DMC_SENS_TORQUE) d.nsens_rne++;
+      if (ty == DMC_SENS_TOUCH) d.nsens_touch++;
+    }
+  }
   d.fluid = (m.opt_density > 0 || m.opt_viscosity > 0) ? 1 : 0;
   for (int w = 0; w < m.nwrap; w++) {
     const int j = m.wrap_objid[w];
