@@ -2,7 +2,7 @@
 // poses, the headlight shading and the analytic textures.  Everything here is plain C++ on one pixel or one camera, so that the same text
 // builds for the device (camera_kernels.hip) and for the host (tests/emu/camera_emu.cpp).
 //
-// The rays are the ones rangefinder sensors cast (step_core.h ray_geom / ray_geom_any: planes front-side only and finite
+// The rays are the ones rangefinder sensors cast (step_geom.h ray_geom / ray_geom_any: planes front-side only and finite
 // where their half-sizes are positive, a ray that starts inside a box leaves through a face).  Those functions take a
 // world-frame pose and transform the ray themselves; a camera shares one origin between all its pixels, so the render
 // kernel transforms once per (camera, geom) -- lp = Rg' (cam_pos - geom_pos), M = Rg' Rcam -- and the closed forms are

@@ -21,40 +21,13 @@
 // column-oriented substitution), so that the fp64 instantiation tracks the
 // oracle to rounding noise; reductions over constraint rows are the exception.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#ifdef DMC_HOST_EMU
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#endif
-
 #include "../../include/dmc_model_layout.h"
 #include "step_layout.h"
-
-#ifdef DMC_HOST_EMU
-#define DMC_DEV inline
-#define DMC_FN inline
-#define DMC_LDS
-#define DMC_GLB
-// (host build: a counter -- how many wave-level fences one step executes is what a match on several waves would have to
-// turn into workgroup barriers: scripts/multiwave_probe.py)
-#define DMC_WSYNC() ((void)++dmc_emu_wsync_count)
-static long long dmc_emu_wsync_count = 0;
-#else
-#define DMC_DEV __device__ __forceinline__
-// out-of-line device functions (one copy of the code for all call sites) taking
-// explicitly LDS-qualified pointers so that they still compile to ds_* ops
-#define DMC_FN __device__ __attribute__((noinline, not_tail_called))
-#define DMC_LDS __attribute__((address_space(3)))
-#define DMC_GLB __attribute__((address_space(1)))   // the per-env global scratch: global_load / global_store, not flat
-#define DMC_WSYNC()                                             \
-  do {                                                          \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      \
-    __builtin_amdgcn_wave_barrier();                            \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      \
-  } while (0)
-#endif
+#include "step_defs.h"
+#include "step_math.h"
+#include "step_lanes.h"
+#include "step_dense.h"
+#include "step_geom.h"
 
 namespace dmc {
 #ifdef DMC_HOST_EMU
@@ -158,673 +131,6 @@ struct StepIO {
 #ifndef DMC_STATIC_FEATURES
 #define DMC_STATIC_FEATURES 1
 #endif
-// ---------------------------------------------------------------------------
-// scalar math (expression order mirrors the oracle)
-// ---------------------------------------------------------------------------
-template <typename T> DMC_DEV T t_sqrt(T x) { return (T)sqrt((double)x); }
-template <> DMC_DEV float t_sqrt<float>(float x) { return sqrtf(x); }
-// 1 / sqrt(x) for the Cholesky pivots.  fp32: the hardware reciprocal square root (v_rsq_f32, 1 ulp) instead of a
-// correctly rounded sqrt followed by a correctly rounded division -- ~25 instructions less on the dependent chain of
-// every column (a fifth of the 62 x 62 factorisation); fp64 keeps the exact sequence the oracle uses.
-template <typename T> DMC_DEV T t_rsqrt(T x) { return 1 / t_sqrt(x); }
-#if !defined(DMC_HOST_EMU) && !defined(DMC_EXACT_RSQ)
-template <> DMC_DEV float t_rsqrt<float>(float x) { return __builtin_amdgcn_rsqf(x); }
-#endif
-template <typename T> DMC_DEV T t_sin(T x) { return (T)sin((double)x); }
-template <> DMC_DEV float t_sin<float>(float x) { return sinf(x); }
-template <typename T> DMC_DEV T t_cos(T x) { return (T)cos((double)x); }
-template <> DMC_DEV float t_cos<float>(float x) { return cosf(x); }
-template <typename T> DMC_DEV T t_pow(T x, T y) { return (T)pow((double)x, (double)y); }
-template <> DMC_DEV float t_pow<float>(float x, float y) { return powf(x, y); }
-template <typename T> DMC_DEV T t_exp(T x) { return (T)exp((double)x); }
-template <typename T> DMC_DEV T t_atan2(T y, T x) { return (T)atan2((double)y, (double)x); }
-template <> DMC_DEV float t_atan2<float>(float y, float x) { return atan2f(y, x); }
-template <typename T> DMC_DEV T t_fmod(T x, T y) { return (T)fmod((double)x, (double)y); }
-template <> DMC_DEV float t_fmod<float>(float x, float y) { return fmodf(x, y); }
-template <> DMC_DEV float t_exp<float>(float x) { return expf(x); }
-// Correctly rounded fp32 division / square root whatever the build's fp32 division mode (step_kernels_f32 is compiled
-// with the 2.5-ulp hardware forms): for the few places whose branch decisions sit on an absolute 1e-10 (the PGS block
-// updates) and are not on the hot path of any BASELINE configuration.
-template <typename T> DMC_DEV T t_div_exact(T a, T b) { return a / b; }
-template <> DMC_DEV float t_div_exact<float>(float a, float b) { return (float)((double)a / (double)b); }
-template <typename T> DMC_DEV T t_sqrt_exact(T x) { return (T)sqrt((double)x); }
-template <typename T> DMC_DEV T t_abs(T x) { return x < 0 ? -x : x; }
-template <typename T> DMC_DEV T t_max(T a, T b) { return a > b ? a : b; }
-template <typename T> DMC_DEV T t_min(T a, T b) { return a < b ? a : b; }
-template <typename T> DMC_DEV bool t_bad(T x) { return !(x == x) || x > (T)DMC_MAXVAL || x < -(T)DMC_MAXVAL; }
-
-template <typename T> DMC_DEV T dot3(const T* a, const T* b) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; }
-template <typename T> DMC_DEV void cross3(T* r, const T* a, const T* b) {
-  T t0 = a[1]*b[2] - a[2]*b[1], t1 = a[2]*b[0] - a[0]*b[2], t2 = a[0]*b[1] - a[1]*b[0];
-  r[0] = t0; r[1] = t1; r[2] = t2;
-}
-template <typename T> DMC_DEV T normalize3(T* v) {
-  T n = t_sqrt(dot3(v, v));
-  if (n < (T)DMC_MINVAL) { v[0] = 1; v[1] = 0; v[2] = 0; }
-  else { T s = 1 / n; v[0] *= s; v[1] *= s; v[2] *= s; }
-  return n;
-}
-template <typename T> DMC_DEV void normalize4(T* q) {
-  T n = t_sqrt(q[0]*q[0] + q[1]*q[1] + q[2]*q[2] + q[3]*q[3]);
-  if (n < (T)DMC_MINVAL) { q[0] = 1; q[1] = q[2] = q[3] = 0; }
-  else if (t_abs(n - 1) > (T)DMC_MINVAL) { T s = 1 / n; q[0] *= s; q[1] *= s; q[2] *= s; q[3] *= s; }
-}
-template <typename T> DMC_DEV void mul_quat(T* r, const T* a, const T* b) {
-  T t0 = a[0]*b[0] - a[1]*b[1] - a[2]*b[2] - a[3]*b[3];
-  T t1 = a[0]*b[1] + a[1]*b[0] + a[2]*b[3] - a[3]*b[2];
-  T t2 = a[0]*b[2] - a[1]*b[3] + a[2]*b[0] + a[3]*b[1];
-  T t3 = a[0]*b[3] + a[1]*b[2] - a[2]*b[1] + a[3]*b[0];
-  r[0] = t0; r[1] = t1; r[2] = t2; r[3] = t3;
-}
-template <typename T> DMC_DEV void quat2mat(T* m, const T* q) {
-  T q00 = q[0]*q[0], q01 = q[0]*q[1], q02 = q[0]*q[2], q03 = q[0]*q[3];
-  T q11 = q[1]*q[1], q12 = q[1]*q[2], q13 = q[1]*q[3];
-  T q22 = q[2]*q[2], q23 = q[2]*q[3], q33 = q[3]*q[3];
-  m[0] = q00 + q11 - q22 - q33; m[4] = q00 - q11 + q22 - q33; m[8] = q00 - q11 - q22 + q33;
-  m[1] = 2*(q12 - q03); m[2] = 2*(q13 + q02);
-  m[3] = 2*(q12 + q03); m[5] = 2*(q23 - q01);
-  m[6] = 2*(q13 - q02); m[7] = 2*(q23 + q01);
-}
-template <typename T> DMC_DEV void mul_mat_vec3(T* r, const T* m, const T* v) {
-  T t0 = m[0]*v[0] + m[1]*v[1] + m[2]*v[2];
-  T t1 = m[3]*v[0] + m[4]*v[1] + m[5]*v[2];
-  T t2 = m[6]*v[0] + m[7]*v[1] + m[8]*v[2];
-  r[0] = t0; r[1] = t1; r[2] = t2;
-}
-template <typename T> DMC_DEV void mul_matT_vec3(T* r, const T* m, const T* v) {
-  T t0 = m[0]*v[0] + m[3]*v[1] + m[6]*v[2];
-  T t1 = m[1]*v[0] + m[4]*v[1] + m[7]*v[2];
-  T t2 = m[2]*v[0] + m[5]*v[1] + m[8]*v[2];
-  r[0] = t0; r[1] = t1; r[2] = t2;
-}
-template <typename T> DMC_DEV void rot_vec_quat(T* r, const T* v, const T* q) {
-  T m[9]; quat2mat(m, q); mul_mat_vec3(r, m, v);
-}
-template <typename T> DMC_DEV void axisangle2quat(T* q, const T* axis, T angle) {
-  // Straight-line on purpose: angle == 0 gives s = 0, c = 1, i.e. the identity MuJoCo
-  // returns early with; an early-out branch (or sincos()'s pointer outputs) makes the
-  // compiler route q through scratch memory.
-  const T s = t_sin(angle * (T)0.5), c = t_cos(angle * (T)0.5);
-  q[0] = c; q[1] = axis[0]*s; q[2] = axis[1]*s; q[3] = axis[2]*s;
-}
-template <typename T> DMC_DEV void quat_integrate(T* quat, const T* vel, T scale) {
-  T tmp[3] = {vel[0], vel[1], vel[2]}, qrot[4];
-  T angle = scale * normalize3(tmp);
-  axisangle2quat(qrot, tmp, angle);
-  normalize4(quat);
-  mul_quat(quat, quat, qrot);
-}
-template <typename T> DMC_DEV void inert_com(T* res, const T* inert, const T* mat, const T* dif, T mass) {
-  T tmp[9];
-  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) tmp[3*r + c] = mat[3*r + c] * inert[c];
-  res[0] = tmp[0]*mat[0] + tmp[1]*mat[1] + tmp[2]*mat[2];
-  res[1] = tmp[3]*mat[3] + tmp[4]*mat[4] + tmp[5]*mat[5];
-  res[2] = tmp[6]*mat[6] + tmp[7]*mat[7] + tmp[8]*mat[8];
-  res[3] = tmp[0]*mat[3] + tmp[1]*mat[4] + tmp[2]*mat[5];
-  res[4] = tmp[0]*mat[6] + tmp[1]*mat[7] + tmp[2]*mat[8];
-  res[5] = tmp[3]*mat[6] + tmp[4]*mat[7] + tmp[5]*mat[8];
-  res[0] += mass * (dif[1]*dif[1] + dif[2]*dif[2]);
-  res[1] += mass * (dif[0]*dif[0] + dif[2]*dif[2]);
-  res[2] += mass * (dif[0]*dif[0] + dif[1]*dif[1]);
-  res[3] -= mass * dif[0]*dif[1];
-  res[4] -= mass * dif[0]*dif[2];
-  res[5] -= mass * dif[1]*dif[2];
-  res[6] = mass*dif[0]; res[7] = mass*dif[1]; res[8] = mass*dif[2];
-  res[9] = mass;
-}
-template <typename T> DMC_DEV void mul_inert_vec(T* res, const T* i, const T* v) {
-  res[0] = i[0]*v[0] + i[3]*v[1] + i[4]*v[2] - i[8]*v[4] + i[7]*v[5];
-  res[1] = i[3]*v[0] + i[1]*v[1] + i[5]*v[2] + i[8]*v[3] - i[6]*v[5];
-  res[2] = i[4]*v[0] + i[5]*v[1] + i[2]*v[2] - i[7]*v[3] + i[6]*v[4];
-  res[3] = i[8]*v[1] - i[7]*v[2] + i[9]*v[3];
-  res[4] = i[6]*v[2] - i[8]*v[0] + i[9]*v[4];
-  res[5] = i[7]*v[0] - i[6]*v[1] + i[9]*v[5];
-}
-template <typename T> DMC_DEV void cross_motion(T* res, const T* vel, const T* v) {
-  res[0] = -vel[2]*v[1] + vel[1]*v[2];
-  res[1] =  vel[2]*v[0] - vel[0]*v[2];
-  res[2] = -vel[1]*v[0] + vel[0]*v[1];
-  res[3] = -vel[2]*v[4] + vel[1]*v[5];
-  res[4] =  vel[2]*v[3] - vel[0]*v[5];
-  res[5] = -vel[1]*v[3] + vel[0]*v[4];
-  res[3] += -vel[5]*v[1] + vel[4]*v[2];
-  res[4] +=  vel[5]*v[0] - vel[3]*v[2];
-  res[5] += -vel[4]*v[0] + vel[3]*v[1];
-}
-template <typename T> DMC_DEV void cross_force(T* res, const T* vel, const T* f) {
-  res[0] = -vel[2]*f[1] + vel[1]*f[2];
-  res[1] =  vel[2]*f[0] - vel[0]*f[2];
-  res[2] = -vel[1]*f[0] + vel[0]*f[1];
-  res[3] = -vel[2]*f[4] + vel[1]*f[5];
-  res[4] =  vel[2]*f[3] - vel[0]*f[5];
-  res[5] = -vel[1]*f[3] + vel[0]*f[4];
-  res[0] += -vel[5]*f[4] + vel[4]*f[5];
-  res[1] +=  vel[5]*f[3] - vel[3]*f[5];
-  res[2] += -vel[4]*f[3] + vel[3]*f[4];
-}
-template <typename T> DMC_DEV T dot_n(const T* a, const T* b, int n) {
-  T s = 0; for (int i = 0; i < n; i++) s += a[i]*b[i]; return s;
-}
-
-// ---------------------------------------------------------------------------
-// group primitives (LPE lanes of one wave)
-// ---------------------------------------------------------------------------
-#ifndef DMC_HOST_EMU
-// DPP cross-lane moves inside a 16-lane row (no LDS traffic, ~VALU latency)
-template <int CTRL> DMC_DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-template <int CTRL> DMC_DEV float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-template <int CTRL> DMC_DEV double dpp_f(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = dpp_i<CTRL>((int)(b & 0xffffffffll)), hi = dpp_i<CTRL>((int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-#endif
-// Exchanges across the 16-lane rows / the 32-lane halves of a wave with the gfx950 row / half swaps
-// (v_permlane16_swap / v_permlane32_swap: VALU moves) instead of a trip through the LDS crossbar (ds_bpermute, what
-// __shfl_xor compiles to): swapping a value with itself leaves {even row's copy, odd row's copy} of each row pair in
-// the two results, whose sum / max is the same in both rows.  Reductions sit on the critical path of every solver
-// iteration (their results feed the next branch), ~25 per Newton iteration.
-#ifndef DMC_HOST_EMU
-struct Pair32 { unsigned a, b; };
-DMC_DEV Pair32 swap16(unsigned x) { const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false); Pair32 p = {r[0], r[1]}; return p; }
-DMC_DEV Pair32 swap32(unsigned x) { const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false); Pair32 p = {r[0], r[1]}; return p; }
-template <int W> DMC_DEV Pair32 swapW(unsigned x) { return W == 16 ? swap16(x) : swap32(x); }
-template <int W> DMC_DEV float xsum(float v) { const Pair32 p = swapW<W>(__float_as_uint(v)); return __uint_as_float(p.a) + __uint_as_float(p.b); }
-template <int W> DMC_DEV int xsum(int v) { const Pair32 p = swapW<W>((unsigned)v); return (int)p.a + (int)p.b; }
-template <int W> DMC_DEV double xsum(double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const Pair32 lo = swapW<W>((unsigned)u), hi = swapW<W>((unsigned)(u >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi.a << 32) | lo.a) + __builtin_bit_cast(double, ((unsigned long long)hi.b << 32) | lo.b);
-}
-template <int W> DMC_DEV int xmax(int v) { const Pair32 p = swapW<W>((unsigned)v); return (int)p.a > (int)p.b ? (int)p.a : (int)p.b; }
-#endif
-// Sum over the LPE lanes of a group; every lane receives the total.  Same
-// pairing tree as an xor butterfly (1, 2, 4, 8 inside a row via DPP quad_perm /
-// row_half_mirror / row_mirror, then 16 and 32 via the row / half swaps).
-template <int LPE, typename V> DMC_DEV V group_sum(V v) {
-#ifndef DMC_HOST_EMU
-  if (LPE >= 2) v += dpp_f<0xB1>(v);    // quad_perm [1,0,3,2]
-  if (LPE >= 4) v += dpp_f<0x4E>(v);    // quad_perm [2,3,0,1]
-  if (LPE >= 8) v += dpp_f<0x141>(v);   // row_half_mirror
-  if (LPE >= 16) v += dpp_f<0x140>(v);  // row_mirror
-  if (LPE >= 32) v = xsum<16>(v);
-  if (LPE >= 64) v = xsum<32>(v);
-#endif
-  return v;
-}
-// value held by lane `k` of each group when k is WAVE-uniform (a loop counter): v_readlane
-// into an SGPR (one per group of the wave) instead of a trip through the LDS crossbar
-#ifndef DMC_HOST_EMU
-DMC_DEV float readlane_t(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-DMC_DEV int readlane_t(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-DMC_DEV double readlane_t(double v, int l) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-#endif
-template <int LPE, typename V> DMC_DEV V wave_bcast(V v, int k) {
-#ifndef DMC_HOST_EMU
-  if (LPE == 64) return readlane_t(v, k);
-  const int g = (int)(__lane_id()) / LPE;   // which group of the wave this lane belongs to
-  V r = readlane_t(v, k);
-#pragma unroll
-  for (int q = 1; q < 64 / LPE; q++) { const V w = readlane_t(v, q*LPE + k); r = g == q ? w : r; }
-  return r;
-#else
-  (void)k; return v;
-#endif
-}
-// The same when every lane that holds something sits in the FIRST 16-lane row of its group (one lane per matrix row of a
-// model with nv <= 16): the gfx90a+ DPP control row_newbcast:k hands lane k of each 16-lane row to all lanes of that row
-// in ONE VALU move (folded into the consuming multiply where the encoding allows) -- against two v_readlane, a trip
-// through two SGPRs and a v_cndmask per value for two environments per wave.  The 9 x 9 factorisations of the cheetah
-// were ~200 instructions of which 135 were these broadcasts; the lanes of the group's other rows receive the value of
-// THEIR row's lane k, which nothing reads (they own no matrix row).  k must be a constant after unrolling.
-#ifndef DMC_HOST_EMU
-template <int CTRL> DMC_DEV float dpp_all(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-template <int CTRL> DMC_DEV double dpp_all(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xF, 0xF, true), hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// (every lane of a row_newbcast has a source lane: bound_ctrl spares the move that would initialise the "old" value)
-template <typename V> DMC_DEV V row_bcast16(V v, int k) {
-  switch (k & 15) {
-    case 0: return dpp_all<0x150>(v); case 1: return dpp_all<0x151>(v); case 2: return dpp_all<0x152>(v); case 3: return dpp_all<0x153>(v);
-    case 4: return dpp_all<0x154>(v); case 5: return dpp_all<0x155>(v); case 6: return dpp_all<0x156>(v); case 7: return dpp_all<0x157>(v);
-    case 8: return dpp_all<0x158>(v); case 9: return dpp_all<0x159>(v); case 10: return dpp_all<0x15A>(v); case 11: return dpp_all<0x15B>(v);
-    case 12: return dpp_all<0x15C>(v); case 13: return dpp_all<0x15D>(v); case 14: return dpp_all<0x15E>(v); default: return dpp_all<0x15F>(v);
-  }
-}
-#endif
-// broadcast of matrix row k's value among the N <= LPE row-holding lanes of a group
-template <int LPE, int N, typename V> DMC_DEV V bcast_rows(V v, int k) {
-#if !defined(DMC_HOST_EMU) && !defined(DMC_NO_ROW_NEWBCAST)
-  if constexpr (N <= 16 && LPE >= 16) return row_bcast16(v, k);
-#endif
-  return wave_bcast<LPE>(v, k);
-}
-template <int LPE> DMC_DEV int group_max(int v) {
-#ifndef DMC_HOST_EMU
-  int w;
-  if (LPE >= 2) { w = dpp_i<0xB1>(v); v = w > v ? w : v; }
-  if (LPE >= 4) { w = dpp_i<0x4E>(v); v = w > v ? w : v; }
-  if (LPE >= 8) { w = dpp_i<0x141>(v); v = w > v ? w : v; }
-  if (LPE >= 16) { w = dpp_i<0x140>(v); v = w > v ? w : v; }
-  if (LPE >= 32) v = xmax<16>(v);
-  if (LPE >= 64) v = xmax<32>(v);
-#endif
-  return v;
-}
-// exclusive prefix sum over the group; *total receives the group sum.  Hillis-Steele inside a 16-lane row with DPP
-// row shifts (zeros shifted in), then the row totals travel with row_bcast:15 / row_bcast:31 -- no LDS crossbar trips
-// (__shfl_up is a ds_bpermute: six dependent ones per scan).
-template <int LPE> DMC_DEV int group_scan(int v, int lane, int* total) {
-#ifndef DMC_HOST_EMU
-  int inc = v;
-  (void)lane;
-  if (LPE >= 2) inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);    // row_shr:1
-  if (LPE >= 4) inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);    // row_shr:2
-  if (LPE >= 8) inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);    // row_shr:4
-  if (LPE >= 16) inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);   // row_shr:8
-  if (LPE >= 32) inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1, 3
-  if (LPE >= 64) inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2, 3
-  *total = wave_bcast<LPE>(inc, LPE - 1);
-  return inc - v;
-#else
-  (void)lane; *total = v; return 0;
-#endif
-}
-
-// ---------------------------------------------------------------------------
-// out-of-line LDS routines shared by several call sites
-// ---------------------------------------------------------------------------
-// Symmetric n x n matrices (the factor of M, H = M + J'DJ and its factor) are stored as their lower
-// triangle packed BY COLUMNS: entry (i, j), i >= j, lives at tri_c0(j, n) + i - j.  Column k is
-// contiguous, and the entries a right-looking Cholesky still has to touch at step k are a suffix.
-DMC_DEV int tri_c0(int j, int n) { return j*n - ((j*(j - 1)) >> 1); }
-DMC_DEV int tri_at(int i, int j, int n) { return tri_c0(j, n) + i - j; }
-// inverse of tri_at for a packed index t of an m x m triangle: column j and row i
-DMC_DEV void tri_unrank(int t, int m, int* i, int* j) {
-  const float b = (float)(2*m + 1);
-  int c = (int)((b - sqrtf(b*b - 8.0f*(float)t)) * 0.5f);
-  c = c < 0 ? 0 : (c > m - 1 ? m - 1 : c);
-  if (tri_c0(c, m) > t) c--;
-  else if (c + 1 < m && tri_c0(c + 1, m) <= t) c++;
-  *j = c; *i = c + (t - tri_c0(c, m));
-}
-// In-place Cholesky of a packed lower triangle, same operation order as the oracle.  On exit: strict
-// lower part = L, diagonal = 1/L[k][k].  Two wave fences per column: scale column k, then every
-// remaining entry (i, j), j > k, is updated by one lane with  A[i][j] -= L[i][k] L[j][k].
-// a - b c: in the fp32 kernels ONE fused operation, said explicitly -- left to the contraction pass, the SLP vectoriser first
-// pairs the products of neighbouring columns into v_pk_mul_f32 and the fusion is lost (two moves, a packed product and two
-// subtractions where two FMAs do); in fp64 the two roundings of the oracle.
-// (FUSE: the small row routines, N <= 16; the larger ones keep the expression the compiler has always seen -- on the 27-dof
-// model the explicit form bought nothing and moved the mean iteration count, profiles/r05_s7_ab_large_models.log)
-template <bool FUSE, typename T> DMC_DEV T nmsub(T a, T b, T c) {
-#ifndef DMC_HOST_EMU
-  if constexpr (FUSE && sizeof(T) == 4) return __builtin_fmaf(-b, c, a);
-#endif
-  return a - b * c;
-}
-#ifndef DMC_HOST_EMU
-// Row-per-lane factor -> the packed triangle (column j at tri_c0(j, N), rows j .. N-1): lane i holds (i, j) for j <= i.
-// Stored WITHOUT a predicate per column: the columns go out last to first, and a lane above the diagonal (i < j) aims
-// its don't-care value at tri_c0(j, N) + i - j -- a slot of an EARLIER column (>= 0 because tri_c0(j, N) >= j), which that
-// column's own store, issued later by the same wave, overwrites with the entry that belongs there.  One exec mask for
-// the N row-holding lanes instead of a compare / mask / branch / restore sequence per column (9 x 8 instructions on the
-// 9-dof model, a quarter of the factorisation).
-template <typename T, int N> DMC_DEV void store_factor_rows(DMC_LDS T* A, const T* a, int lane) {
-  if (lane < N) {
-#pragma unroll
-    for (int j = N - 1; j >= 0; j--) { A[tri_c0(j, N) + lane - j] = a[j]; asm volatile("" ::: "memory"); }      // (in THIS order: to one lane the nine addresses are unrelated)
-  }
-}
-#endif
-template <typename T, int LPE>
-DMC_FN void chol_factor_lds(DMC_LDS T* A, int n, int lane) {
-  const int ntri = (n*(n + 1)) >> 1;
-  for (int k = 0; k < n; k++) {
-    DMC_WSYNC();
-    const int ck = tri_c0(k, n);
-    T akk = A[ck];
-    if (akk < (T)DMC_MINVAL) akk = (T)DMC_MINVAL;
-    const T inv = t_rsqrt(akk);
-    for (int i = k + 1 + lane; i < n; i += LPE) A[ck + i - k] *= inv;
-    DMC_WSYNC();
-    if (lane == 0) A[ck] = inv;
-    const int c1 = ck + n - k, m = n - k - 1;   // trailing (n-k-1) x (n-k-1) triangle starts at c1
-    for (int t = lane; t < ntri - c1; t += LPE) {
-      int ii, jj;
-      tri_unrank(t, m, &ii, &jj);
-      A[c1 + t] -= A[ck + 1 + ii] * A[ck + 1 + jj];
-    }
-  }
-  DMC_WSYNC();
-}
-// Model-specialised kernels know nv at compile time: lane i of the group keeps row i of the
-// matrix in N registers, pivots and scaled columns travel by v_readlane -- no LDS round trip
-// and no fence per column (N = 27: ~1.1 k instructions instead of 27 fenced LDS sweeps).
-// Same arithmetic per entry, in the same order, as chol_factor_lds: identical results.
-#ifndef DMC_HOST_EMU
-template <typename T, int LPE, int N>
-DMC_FN void chol_factor_rows(DMC_LDS T* A, int lane) {
-  static_assert(N >= 1 && N <= LPE, "one lane per matrix row");
-  DMC_WSYNC();
-  T a[N];
-  const bool own = lane < N;
-#pragma unroll
-  for (int j = 0; j < N; j++) {      // (N <= 16: unpredicated loads, the value selected afterwards -- a predicated load costs an exec-mask round trip each)
-    if constexpr (N > 16) a[j] = (own && j <= lane) ? A[tri_c0(j, N) + lane - j] : (T)0;      // (27 dofs: 3 % faster predicated -- half the reads)
-    else {
-      const int i_ = own && j <= lane ? lane : j;
-      const T v = A[tri_c0(j, N) + i_ - j];
-      a[j] = (own && j <= lane) ? v : (T)0;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    T akk = bcast_rows<LPE, N>(a[k], k);
-    if (akk < (T)DMC_MINVAL) akk = (T)DMC_MINVAL;
-    const T inv = t_rsqrt(akk);
-    const T lik = a[k] * inv;
-#pragma unroll
-    for (int j = k + 1; j < N; j++) { const T ljk = bcast_rows<LPE, N>(lik, j); a[j] = nmsub<(N <= 16)>(a[j], lik, ljk); }
-    a[k] = lane == k ? inv : lik;
-  }
-  store_factor_rows<T, N>(A, a, lane);
-  DMC_WSYNC();
-}
-#endif
-// The same factorisation on the MATRIX CORES for the large fp32 models (32 < N <= 64, one environment per wave): blocked
-// right-looking U'U on 16 x 16 tiles held in the accumulator layout of v_mfma_f32_16x16x4_f32 -- lane 16 g + c, register r
-// of a tile = its element (4 g + r, c).  Fed as BOTH operands, register by register, two tiles X, Y in that layout give
-// X'Y (operand A reads lane l as A[l & 15][l >> 4], operand B as B[l >> 4][l & 15]: register r of X is X'[i][4 k + r],
-// register r of Y is Y[4 k + r][j], and the four instructions r = 0 .. 3 cover the sixteen k) -- which is the trailing update
-// A_ij -= U_ki' U_kj of the upper-triangular form, in place, with no layout conversion: 40 matrix instructions do what
-// 1 891 v_readlane + v_fma pairs do in chol_factor_rows<62>.  The sixteen columns of a diagonal tile are eliminated on
-// the vector ALU, together with the rest of their block row (which is the panel solve): the pivot comes by v_readlane,
-// the column below it by DPP row_newbcast (the diagonal tile is kept whole and symmetric, so column C0 of a row group is
-// lane C0 of that row group), the scaled pivot row reaches the other row groups through one ds_bpermute per tile; rows at
-// or above the pivot get a zero multiplier instead of a predicate.  Rows / columns N .. 63 enter as the identity.  The
-// packed triangle leaves as chol_factor_rows leaves it (scaled columns, 1 / L_kk on the diagonal); the sums run in another
-// order (the products of a tile update are added k-slot by k-slot), so the factor differs from chol_factor_rows' by
-// rounding.  Measured (scripts/chol_mfma_probe.hip, profiles/r06_chol_mfma_probe.log): 2 191 instructions against 5 118,
-// 17.0 k cycles per factorisation against 38.9 k with five waves per CU.
-#if !defined(DMC_HOST_EMU)
-typedef float dmc_f4 __attribute__((ext_vector_type(4)));
-template <int N> struct CholTiles {
-  static constexpr int NB = (N + 15) / 16;
-  struct LaneInfo { int g, col4, lane; float fgt[3]; };      // fgt[q] = 1 where the lane's row group g > q, else 0
-  // the value of the lane of the same column in row group GC, for every row group: on the diagonal tile (the critical
-  // chain) by two VALU swaps, on the rest of the block row through the LDS crossbar (off the chain; 18.5 k -> 15.3 k cycles)
-  template <int GC, bool DIAG> static DMC_DEV float bcast_rowgroup(float x, int col4) {
-    if constexpr (!DIAG) return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(col4 + 64 * GC, __builtin_bit_cast(int, x)));
-    else {
-      const unsigned u = __builtin_bit_cast(unsigned, x);
-      const auto h = __builtin_amdgcn_permlane32_swap(u, u, false, false);      // h[0]: row groups (0 1 0 1), h[1]: (2 3 2 3)
-      const unsigned y = GC < 2 ? h[0] : h[1];
-      const auto q = __builtin_amdgcn_permlane16_swap(y, y, false, false);      // q[0]: the even group everywhere, q[1]: the odd
-      return __builtin_bit_cast(float, (GC & 1) ? q[1] : q[0]);
-    }
-  }
-  template <int K, int C0> static DMC_DEV void eliminate_column(dmc_f4 (&t)[NB][NB], const LaneInfo& tl) {
-    constexpr int GC = C0 >> 2, RC = C0 & 3;
-    dmc_f4& D = t[K][K];
-    const float inv = __builtin_amdgcn_rsqf(__builtin_amdgcn_fmed3f(readlane_t(D[RC], 16 * GC + C0), (float)DMC_MINVAL, __builtin_inff()));
-    // the column below the pivot, scaled; rows at or above the pivot row get a zero multiplier, folded into the scale
-    // (4 g + r > C0  <=>  r > RC ? g >= GC : g > GC)
-    const float inv_ge = GC == 0 ? inv : inv * tl.fgt[GC > 0 ? GC - 1 : 0];
-    const float inv_gt = GC == 3 ? 0.f : inv * tl.fgt[GC < 3 ? GC : 0];
-    float ui[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) ui[r] = (GC == 3 && r <= RC) ? 0.f : dpp_all<0x150 + C0>(D[r]) * (r > RC ? inv_ge : inv_gt);
-    const float scale = tl.g == GC ? inv : 1.f;      // the pivot row itself is scaled in place
-#pragma unroll
-    for (int j = K; j < NB; j++) {
-      dmc_f4& P = t[K][j];
-      P[RC] = P[RC] * scale;
-      const float X = j == K ? bcast_rowgroup<GC, true>(P[RC], tl.col4) : bcast_rowgroup<GC, false>(P[RC], tl.col4);
-#pragma unroll
-      for (int r = 0; r < 4; r++) if (!(GC == 3 && r <= RC)) P[r] = P[r] - ui[r] * X;
-    }
-    D[RC] = (tl.lane == 16 * GC + C0) ? inv : D[RC];      // the packed form keeps 1 / L_kk on the diagonal
-  }
-  template <int K, int C0> struct Columns {
-    static DMC_DEV void run(dmc_f4 (&t)[NB][NB], const LaneInfo& tl) {
-      if constexpr (16 * K + C0 < N) eliminate_column<K, C0>(t, tl);      // (the columns past N are the identity's)
-      if constexpr (C0 + 1 < 16) Columns<K, C0 + 1>::run(t, tl);
-    }
-  };
-  template <int K> static DMC_DEV void block_column(dmc_f4 (&t)[NB][NB], const LaneInfo& tl) {
-    Columns<K, 0>::run(t, tl);
-#pragma unroll
-    for (int i = K + 1; i < NB; i++) {
-      const dmc_f4 nx = -t[K][i];
-#pragma unroll
-      for (int j = i; j < NB; j++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(nx[r], t[K][j][r], t[i][j], 0, 0, 0);
-      }
-    }
-    if constexpr (K + 1 < NB) block_column<K + 1>(t, tl);
-  }
-  static DMC_DEV constexpr int c0(int j) { return j * N - ((j * (j - 1)) >> 1); }      // tri_c0(j, N)
-  // Packed index of element (R, C), R <= C, of tile (bi, bj), register r, for the lane (g, c): tri_c0(R) + C - R with
-  // R = R0 + G (R0 = 16 bi + r, G = 4 g)  =  [tri_c0(R0) + 16 bj - R0] + [tri_c0(G) - G + c] - R0 G
-  static DMC_DEV void factor(DMC_LDS float* A, int lane) {
-    static_assert(N > 32 && N <= 64, "three or four tiles a side (store()'s spare slot is an entry of column 16 + c: N >= 32; below 33 dofs the row form is as fast)");
-    const int g = lane >> 4, c = lane & 15, G = 4 * g;
-    LaneInfo tl; tl.g = g; tl.col4 = 4 * c; tl.lane = lane;
-#pragma unroll
-    for (int q = 0; q < 3; q++) tl.fgt[q] = g > q ? 1.f : 0.f;
-    const int up = c0(G) - G + c;                      // lane part of the upper-triangle index
-    const int tc = ((c * (2 * N + 1 - c)) >> 1) - c;   // tri_c0(c) - c: lane part of the mirrored (lower-triangle) index
-    dmc_f4 t[NB][NB];
-#pragma unroll
-    for (int bi = 0; bi < NB; bi++)
-#pragma unroll
-      for (int bj = bi; bj < NB; bj++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int R0 = 16 * bi + r;
-          int at = c0(R0) + 16 * bj - R0 + up - R0 * G;
-          if (bi == bj) {      // the diagonal tiles enter whole (symmetric): below the diagonal the mirrored entry
-            const int low = c0(16 * bi) + tc - 16 * bi * c + R0 - 16 * bi + G;
-            at = (G + r <= c) ? at : low;
-          }
-          float v = A[at];      // (unpredicated: an index past the triangle reads a neighbouring array, the value is dropped)
-          if (16 * bj + 15 >= N) { const bool in = (16 * bj + c < N) && (bi < bj || 16 * bi + G + r < N); v = in ? v : ((bi == bj && G + r == c) ? 1.f : 0.f); }
-          t[bi][bj][r] = v;
-        }
-    block_column<0>(t, tl);
-    // stores: an entry that does not exist (below the diagonal of a diagonal tile, past column N) aims at the slot of the
-    // lane's entry (row 4 g, column 16 + c) -- which exists for every lane and is stored LAST, over whatever landed there
-    const int safe = 16 + up;
-#pragma unroll
-    for (int bi = NB - 1; bi >= 0; bi--)
-#pragma unroll
-      for (int bj = NB - 1; bj >= bi; bj--)
-#pragma unroll
-        for (int r = 3; r >= 0; r--) {
-          const int R0 = 16 * bi + r;
-          int at = c0(R0) + 16 * bj - R0 + up - R0 * G;
-          bool ok = true;
-          if (bi == bj) ok = G + r <= c;
-          if (16 * bj + 15 >= N) ok = ok && (16 * bj + c < N);
-          if (bi == bj || 16 * bj + 15 >= N) at = ok ? at : safe;
-          if (!(bi == 0 && bj == 1 && r == 0)) A[at] = t[bi][bj][r];
-        }
-    asm volatile("" ::: "memory");
-    A[safe] = t[0][1][0];
-  }
-};
-template <int LPE, int N>
-DMC_FN void chol_factor_tiles(DMC_LDS float* A, int lane) {
-  static_assert(LPE == 64, "one environment per wave");
-  DMC_WSYNC();
-  CholTiles<N>::factor(A, lane);
-  DMC_WSYNC();
-}
-#endif
-// Substitution for model-specialised kernels: lane i loads its row and its column of L up
-// front (all loads in flight together), then both sweeps run on registers and v_readlane --
-// no LDS access inside the 2 N dependent steps.  Same operations as chol_solve_lds.
-#ifndef DMC_HOST_EMU
-template <typename T, int LPE, int N>
-DMC_FN void chol_solve_rows(DMC_LDS T* x, const DMC_LDS T* Lm, const DMC_LDS T* b, int lane) {
-  static_assert(N >= 1 && N <= LPE, "one lane per unknown");
-  const int i = lane;
-  const bool own = i < N;
-  const int ci = tri_c0(own ? i : 0, N);
-  T row[N], col[N];
-#pragma unroll
-  for (int k = 0; k < N; k++) {      // (N <= 16: unpredicated loads from in-range addresses, the values selected afterwards)
-    if constexpr (N > 16) { row[k] = (own && k < i) ? Lm[tri_c0(k, N) + i - k] : (T)0; col[k] = (own && k > i) ? Lm[ci + k - i] : (T)0; }
-    else {
-      const T r_ = Lm[tri_c0(k, N) + ((own && k < i) ? i - k : 0)], c_ = Lm[ci + ((own && k > i) ? k - i : 0)];
-      row[k] = (own && k < i) ? r_ : (T)0; col[k] = (own && k > i) ? c_ : (T)0;
-    }
-  }
-  const T dinv_ = Lm[ci], b_ = b[own ? i : 0];
-  const T dinv = own ? dinv_ : (T)0;      // 1 / L[i][i]
-  T sreg = own ? b_ : (T)0;
-  // Step k needs x_k = s_k / L[k][k]: every lane forms its own s_i * dinv_i (one VALU op, and lane k's is the value),
-  // ONE cross-lane read fetches it, and the update is an unconditional FMA -- row[k] / col[k] are zeros where the
-  // step does not reach, so lane k keeps its finished s_k and its x_k is s_k * dinv_k again after the loop.  Three
-  // instructions per step instead of ~20 (two broadcasts, a scalar product moved back to a VGPR, a write-lane and two
-  // predicated updates: 2 603 instructions for N = 62, 8 % of the 62-dof step).  The same products and differences as
-  // before, bit for bit.
-#pragma unroll
-  for (int k = 0; k < N; k++) { const T xk = bcast_rows<LPE, N>(sreg*dinv, k); sreg = nmsub<(N <= 16)>(sreg, row[k], xk); }
-  sreg = sreg*dinv;
-#pragma unroll
-  for (int k = N - 1; k >= 0; k--) { const T xk = bcast_rows<LPE, N>(sreg*dinv, k); sreg = nmsub<(N <= 16)>(sreg, col[k], xk); }
-  if (own) x[i] = sreg*dinv;
-  DMC_WSYNC();
-}
-#endif
-// ---- block diagonal over the kinematic trees (StepDims::treemax) ------------------------------------------------
-// M -- and H = M + J'DJ as long as no constraint row moves two trees -- is block diagonal over the kinematic trees of a
-// multi-body scene (soccer 2v2: five trees of six dofs).  The row-per-lane routines above run the N columns one after
-// the other, N (N + 1) / 2 cross-lane broadcasts + FMAs, of which all but the in-tree ones multiply exact zeros; a lone
-// wave per SIMD pays ~9 cycles per instruction, so the 30 x 30 factorisation was 16 k cycles, 8 % of the soccer step, and
-// each substitution 11 k.  Here every tree eliminates ITS column kk = 0 .. TM-1 at the same time: the pivot lane differs
-// per tree, so the broadcasts are per-lane-addressed (ds_bpermute) instead of v_readlane: TM (TM + 1) / 2 of them for
-// the whole matrix.  Entry for entry the same operations in the same order as chol_factor_rows / chol_solve_rows --
-// what is skipped is  a - 0 * x -- so the results are bit-identical.  t0 / t1: first dof / 1 + last dof of the lane's
-// tree.  One environment per wave (LPE = 64).
-#ifndef DMC_HOST_EMU
-DMC_DEV float lane_read(float v, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v))); }
-DMC_DEV double lane_read(double v, int src) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)u);
-  const unsigned hi = (unsigned)__builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)(u >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-template <typename T, int LPE, int N, int TM>
-DMC_FN void chol_factor_trees(DMC_LDS T* A, int lane, int t0, int t1) {
-  static_assert(LPE == 64 && N <= LPE, "one lane per matrix row, one environment per wave");
-  DMC_WSYNC();
-  T a[TM];
-  const bool own = lane < N;
-#pragma unroll
-  for (int kk = 0; kk < TM; kk++) { const int j = t0 + kk; a[kk] = (own && j <= lane) ? A[tri_c0(j, N) + lane - j] : (T)0; }
-#pragma unroll
-  for (int kk = 0; kk < TM; kk++) {
-    const int src = t0 + kk;
-    T akk = lane_read(a[kk], src);
-    if (akk < (T)DMC_MINVAL) akk = (T)DMC_MINVAL;
-    const T inv = t_rsqrt(akk);
-    const T lik = (own && src < t1) ? a[kk] * inv : (T)0;      // (a tree with fewer than TM dofs sits these columns out)
-#pragma unroll
-    for (int jj = kk + 1; jj < TM; jj++) { const T ljk = lane_read(lik, t0 + jj); a[jj] = a[jj] - lik * ljk; }
-    a[kk] = lane == src ? inv : lik;
-  }
-#pragma unroll
-  for (int kk = 0; kk < TM; kk++) { const int j = t0 + kk; if (own && j <= lane) A[tri_c0(j, N) + lane - j] = a[kk]; }
-  DMC_WSYNC();
-}
-template <typename T, int LPE, int N, int TM>
-DMC_FN void chol_solve_trees(DMC_LDS T* x, const DMC_LDS T* Lm, const DMC_LDS T* b, int lane, int t0, int t1) {
-  static_assert(LPE == 64 && N <= LPE, "one lane per unknown, one environment per wave");
-  const int i = lane;
-  const bool own = i < N;
-  const int ci = tri_c0(own ? i : 0, N);
-  T row[TM], col[TM], dk[TM];
-  const T dinv = own ? Lm[ci] : (T)0;      // 1 / L[i][i]
-#pragma unroll
-  for (int kk = 0; kk < TM; kk++) {
-    const int k = t0 + kk;
-    row[kk] = (own && k < i) ? Lm[tri_c0(k, N) + i - k] : (T)0;
-    col[kk] = (own && k > i && k < t1) ? Lm[ci + k - i] : (T)0;
-    dk[kk] = lane_read(dinv, k);
-  }
-  T sreg = own ? b[i] : (T)0;
-#pragma unroll
-  for (int kk = 0; kk < TM; kk++) {
-    const int k = t0 + kk;
-    const T xk = lane_read(sreg, k) * dk[kk];
-    if (i == k) sreg = xk;
-    if (i > k && own) sreg -= row[kk]*xk;
-  }
-#pragma unroll
-  for (int kk = TM - 1; kk >= 0; kk--) {
-    const int k = t0 + kk;
-    const T xk = lane_read(sreg, k) * dk[kk];
-    if (i == k) sreg = xk;
-    if (i < k && k < t1 && own) sreg -= col[kk]*xk;
-  }
-  if (own) x[i] = sreg;
-  DMC_WSYNC();
-}
-#endif
-// x = (L L')^-1 b (x may alias b); Lm as produced by chol_factor_lds
-//   n <= LPE : lane i carries x[i] in a register; the pivot value travels by a
-//              cross-lane broadcast, no LDS round trip, no fence inside the loops.
-template <typename T, int LPE>
-DMC_FN void chol_solve_lds(DMC_LDS T* x, const DMC_LDS T* Lm, const DMC_LDS T* b, int n, int lane) {
-  if (n <= LPE && LPE > 1) {
-    const int i = lane;
-    const int ci = tri_c0(i < n ? i : 0, n);
-    T sreg = i < n ? b[i] : (T)0;
-    for (int k = 0; k < n; k++) {
-      const int ck = tri_c0(k, n);
-      const T lik = (i > k && i < n) ? Lm[ck + i - k] : (T)0;
-      const T xk = wave_bcast<LPE>(sreg, k) * Lm[ck];
-      if (i == k) sreg = xk;
-      if (i > k && i < n) sreg -= lik*xk;
-    }
-    for (int k = n - 1; k >= 0; k--) {
-      const T lki = i < k ? Lm[ci + k - i] : (T)0;
-      const T xk = wave_bcast<LPE>(sreg, k) * Lm[tri_c0(k, n)];
-      if (i == k) sreg = xk;
-      if (i < k) sreg -= lki*xk;
-    }
-    if (i < n) x[i] = sreg;
-    DMC_WSYNC();
-    return;
-  }
-  for (int i = lane; i < n; i += LPE) x[i] = b[i];
-  DMC_WSYNC();
-  for (int k = 0; k < n; k++) {
-    const int ck = tri_c0(k, n);
-    const T xk = x[k] * Lm[ck];
-    DMC_WSYNC();
-    if (lane == 0) x[k] = xk;
-    for (int i = k + 1 + lane; i < n; i += LPE) x[i] -= Lm[ck + i - k]*xk;
-    DMC_WSYNC();
-  }
-  for (int k = n - 1; k >= 0; k--) {
-    const T xk = x[k] * Lm[tri_c0(k, n)];
-    DMC_WSYNC();
-    if (lane == 0) x[k] = xk;
-    for (int i = lane; i < k; i += LPE) x[i] -= Lm[tri_c0(i, n) + k - i]*xk;
-    DMC_WSYNC();
-  }
-}
 // line-search evaluation: cost / derivatives of the piecewise quadratic at alpha
 template <typename T> struct LSPoint { T alpha, cost, d0, d1; };
 // fp32: the line search works on the cost RELATIVE to alpha = 0.  Its points are only ever compared with each other,
@@ -1743,420 +1049,10 @@ struct StepCore {
   }
 
   // ---- collision (mj_collision over the static candidate pair list) -------------
-  DMC_DEV static void make_frame(T* f) {
-    normalize3(f);
-    if (t_sqrt(dot3(f + 3, f + 3)) < (T)0.5) {
-      f[3] = f[4] = f[5] = 0;
-      if (f[1] < (T)0.5 && f[1] > (T)-0.5) f[4] = 1; else f[5] = 1;
-    }
-    T t = dot3(f, f + 3);
-    f[3] -= t*f[0]; f[4] -= t*f[1]; f[5] -= t*f[2];
-    normalize3(f + 3);
-    cross3(f + 6, f, f + 3);
-  }
-  struct Hit { T dist, pos[3], nrm[3]; };
-  DMC_DEV static int plane_sphere(Hit* h, T margin, const T* ppos, const T* nrm, const T* spos, T radius) {
-    T dif[3] = {spos[0] - ppos[0], spos[1] - ppos[1], spos[2] - ppos[2]};
-    T dist = dot3(dif, nrm) - radius;
-    if (dist > margin) return 0;
-    h->dist = dist;
-    for (int k = 0; k < 3; k++) { h->pos[k] = spos[k] - nrm[k]*(radius + dist*(T)0.5); h->nrm[k] = nrm[k]; }
-    return 1;
-  }
-  DMC_DEV static int sphere_sphere(Hit* h, T margin, const T* p1, T r1, const T* p2, T r2) {
-    T dif[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
-    T cdist = t_sqrt(dot3(dif, dif));
-    T dist = cdist - r1 - r2;
-    if (dist > margin) return 0;
-    T n[3];
-    if (cdist < (T)DMC_MINVAL) { n[0] = 1; n[1] = n[2] = 0; } else { n[0] = dif[0]/cdist; n[1] = dif[1]/cdist; n[2] = dif[2]/cdist; }
-    h->dist = dist;
-    for (int k = 0; k < 3; k++) { h->pos[k] = p1[k] + n[k]*(r1 + dist*(T)0.5); h->nrm[k] = n[k]; }
-    return 1;
-  }
-  // h[n] = x with every slot index a compile-time constant, so that the hit
-  // buffer stays in registers (a dynamically indexed local array lives in scratch)
-  struct Hits { Hit s0, s1, s2, s3; };
-  DMC_DEV static void sel_hit(Hit& d, const Hit& x, bool c) {
-    d.dist = c ? x.dist : d.dist;
-    for (int k = 0; k < 3; k++) { d.pos[k] = c ? x.pos[k] : d.pos[k]; d.nrm[k] = c ? x.nrm[k] : d.nrm[k]; }
-  }
-  DMC_DEV static void put_hit(Hits* h, int n, const Hit& x) {
-    sel_hit(h->s0, x, n == 0); sel_hit(h->s1, x, n == 1); sel_hit(h->s2, x, n == 2); sel_hit(h->s3, x, n == 3);
-  }
-  // ---- ellipsoid pairs: signed distance = max over unit n of the support-function gap F(n),
-  // Newton iteration on the unit sphere; a capsule is its swept sphere minimised over the axis
-  // parameter (regula falsi on n.axis).  Same iteration, same operation order as the oracle's
-  // "ellipsoid pairs" section; everything lives in registers (constant indexing only).
-  struct Quadric { T c[3], R[9], s[3]; };
-  DMC_DEV static constexpr T ccd_tol() { return sizeof(T) == 8 ? (T)1e-10 : (T)1e-4; }
-  DMC_DEV static constexpr int ccd_maxit() { return sizeof(T) == 8 ? 30 : 12; }
-  DMC_DEV static T quadric_support(const Quadric& q, const T* n, T* g, T* wh) {
-    T w[3];
-    for (int k = 0; k < 3; k++) w[k] = q.s[k]*(q.R[k]*n[0] + q.R[3 + k]*n[1] + q.R[6 + k]*n[2]);
-    const T wn = t_sqrt(dot3(w, w));
-    if (wn < (T)DMC_MINVAL) { g[0] = g[1] = g[2] = 0; wh[0] = wh[1] = wh[2] = 0; return 0; }
-    T v[3];
-    for (int k = 0; k < 3; k++) { wh[k] = w[k]/wn; v[k] = q.s[k]*wh[k]; }
-    mul_mat_vec3(g, q.R, v);
-    return wn;
-  }
-  DMC_DEV static void quadric_curv(const Quadric& q, const T* wh, T wn, const T* t1, const T* t2, T* K) {
-    if (wn < (T)DMC_MINVAL) return;
-    T y1[3], y2[3];
-    for (int k = 0; k < 3; k++) {
-      y1[k] = q.s[k]*(q.R[k]*t1[0] + q.R[3 + k]*t1[1] + q.R[6 + k]*t1[2]);
-      y2[k] = q.s[k]*(q.R[k]*t2[0] + q.R[3 + k]*t2[1] + q.R[6 + k]*t2[2]);
-    }
-    const T a1 = dot3(y1, wh), a2 = dot3(y2, wh);
-    K[0] += (dot3(y1, y1) - a1*a1)/wn; K[1] += (dot3(y1, y2) - a1*a2)/wn; K[2] += (dot3(y2, y2) - a2*a2)/wn;
-  }
-  DMC_DEV static T quadric_gap_value(const Quadric& A, const Quadric& B, const T* n) {
-    T g[3], wh[3], d[3] = {B.c[0] - A.c[0], B.c[1] - A.c[1], B.c[2] - A.c[2]};
-    const T hA = quadric_support(A, n, g, wh), hB = quadric_support(B, n, g, wh);
-    return dot3(n, d) - hA - hB;
-  }
-  DMC_DEV static T quadric_gap(const Quadric& A, const Quadric& B, T* n, T* gA, T* gB) {
-    const T d[3] = {B.c[0] - A.c[0], B.c[1] - A.c[1], B.c[2] - A.c[2]};
-    T F = 0;
-    for (int it = 0; ; it++) {
-      T wA[3], wB[3];
-      const T hA = quadric_support(A, n, gA, wA), hB = quadric_support(B, n, gB, wB);
-      F = dot3(n, d) - hA - hB;
-      if (it >= ccd_maxit()) break;
-      T f[9] = {n[0], n[1], n[2], 0, 0, 0, 0, 0, 0};
-      make_frame(f);
-      const T *t1 = f + 3, *t2 = f + 6;
-      const T grad[3] = {d[0] - gA[0] - gB[0], d[1] - gA[1] - gB[1], d[2] - gA[2] - gB[2]};
-      const T g1 = dot3(t1, grad), g2 = dot3(t2, grad);
-      T K[3] = {F, 0, F};
-      quadric_curv(A, wA, hA, t1, t2, K); quadric_curv(B, wB, hB, t1, t2, K);
-      const T tr = K[0] + K[2];
-      T det = K[0]*K[2] - K[1]*K[1];
-      const T floor_ = (T)1e-3*(hA + hB) + (T)DMC_MINVAL;
-      const T lmin = (T)0.5*(tr - t_sqrt(t_max((T)0, tr*tr - 4*det)));
-      if (lmin < floor_) { const T sh = floor_ - lmin; K[0] += sh; K[2] += sh; det = K[0]*K[2] - K[1]*K[1]; }
-      T d1 = (K[2]*g1 - K[1]*g2)/det, d2 = (K[0]*g2 - K[1]*g1)/det;
-      if (d1*d1 + d2*d2 < ccd_tol()*ccd_tol()) break;
-      T nn[3];
-      for (int ls = 0; ; ls++) {
-        for (int k = 0; k < 3; k++) nn[k] = n[k] + t1[k]*d1 + t2[k]*d2;
-        normalize3(nn);
-        if (ls >= 8 || quadric_gap_value(A, B, nn) >= F) break;
-        d1 *= (T)0.5; d2 *= (T)0.5;
-      }
-      n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2];
-    }
-    return F;
-  }
-  DMC_DEV static void quadric_init_dir(const Quadric& A, const Quadric& B, T* n) {
-    for (int k = 0; k < 3; k++) n[k] = B.c[k] - A.c[k];
-    if (dot3(n, n) < (T)DMC_MINVAL*(T)DMC_MINVAL) { n[0] = 1; n[1] = n[2] = 0; }
-    normalize3(n);
-  }
-  DMC_DEV static int quadric_contact(Hit* h, T margin, const Quadric& A, const Quadric& B, T* n) {
-    T gA[3], gB[3];
-    const T dist = quadric_gap(A, B, n, gA, gB);
-    if (dist > margin) return 0;
-    h->dist = dist;
-    for (int k = 0; k < 3; k++) { h->pos[k] = (T)0.5*((A.c[k] + gA[k]) + (B.c[k] - gB[k])); h->nrm[k] = n[k]; }
-    return 1;
-  }
-  DMC_DEV static Quadric make_quadric(int type, const T* pos, const T* mat, const T* size) {
-    Quadric q;
-    for (int k = 0; k < 3; k++) { q.c[k] = pos[k]; q.s[k] = type == DMC_GEOM_ELLIPSOID ? size[k] : size[0]; }
-    for (int k = 0; k < 9; k++) q.R[k] = mat[k];
-    return q;
-  }
-  // geom 2 is an ellipsoid; geom 1 a plane-less partner (sphere, capsule or ellipsoid)
-  DMC_DEV static int ellipsoid_pair(Hit* h, T margin, int t1, const T* p1, const T* m1, const T* s1,
-                                    const T* p2, const T* m2, const T* s2) {
-    Quadric A = make_quadric(t1 == DMC_GEOM_CAPSULE ? DMC_GEOM_SPHERE : t1, p1, m1, s1);
-    const Quadric B = make_quadric(DMC_GEOM_ELLIPSOID, p2, m2, s2);
-    T n[3];
-    if (t1 != DMC_GEOM_CAPSULE) { quadric_init_dir(A, B, n); return quadric_contact(h, margin, A, B, n); }
-    const T u[3] = {m1[2], m1[5], m1[8]};
-    const T hl = s1[1];
-    T gA[3], gB[3];
-    T tlo = -hl, thi = hl, plo, phi = 0, t;
-    for (int k = 0; k < 3; k++) A.c[k] = p1[k] + u[k]*tlo;
-    quadric_init_dir(A, B, n);
-    quadric_gap(A, B, n, gA, gB); plo = dot3(n, u);
-    if (plo <= 0) t = tlo;
-    else {
-      for (int k = 0; k < 3; k++) A.c[k] = p1[k] + u[k]*thi;
-      quadric_gap(A, B, n, gA, gB); phi = dot3(n, u);
-      if (phi >= 0) t = thi;
-      else {
-        t = 0;
-        int side = 0;
-        for (int it = 0; it < 40; it++) {
-          t = (tlo*phi - thi*plo)/(phi - plo);
-          for (int k = 0; k < 3; k++) A.c[k] = p1[k] + u[k]*t;
-          quadric_gap(A, B, n, gA, gB);
-          const T pt = dot3(n, u);
-          if (t_abs(pt) < ccd_tol() || thi - tlo < ccd_tol()*hl) break;
-          if (pt > 0) { tlo = t; plo = pt; if (side == 1) phi *= (T)0.5; side = 1; }
-          else { thi = t; phi = pt; if (side == -1) plo *= (T)0.5; side = -1; }
-        }
-      }
-    }
-    for (int k = 0; k < 3; k++) A.c[k] = p1[k] + u[k]*t;
-    return quadric_contact(h, margin, A, B, n);
-  }
-  DMC_DEV static int plane_ellipsoid(Hit* h, T margin, const T* p1, const T* nrm, const T* p2, const T* m2, const T* s2) {
-    const Quadric q = make_quadric(DMC_GEOM_ELLIPSOID, p2, m2, s2);
-    T g[3], wh[3];
-    quadric_support(q, nrm, g, wh);
-    const T pt[3] = {p2[0] - g[0], p2[1] - g[1], p2[2] - g[2]};
-    const T dif[3] = {pt[0] - p1[0], pt[1] - p1[1], pt[2] - p1[2]};
-    const T dist = dot3(dif, nrm);
-    if (dist > margin) return 0;
-    h->dist = dist;
-    for (int k = 0; k < 3; k++) { h->pos[k] = pt[k] - nrm[k]*dist*(T)0.5; h->nrm[k] = nrm[k]; }
-    return 1;
-  }
-  // ---- box pairs (sphere-box, capsule-box, box-box): same constructions, same operation order as the
-  // oracle's "box pairs" section.  The clipping polygon is a dynamically indexed local array (scratch
-  // memory); the code is compiled out of models without such pairs (d.nbox == 0).
-  DMC_DEV static int sphere_box_core(Hit* h, T margin, const T* ps, T r, const T* pb, const T* mb, const T* sb) {
-    T dif[3] = {ps[0] - pb[0], ps[1] - pb[1], ps[2] - pb[2]}, cl[3], q[3], nb[3] = {0, 0, 0};
-    mul_matT_vec3(cl, mb, dif);
-    bool outside = false;
-    for (int k = 0; k < 3; k++) { q[k] = t_max(-sb[k], t_min(sb[k], cl[k])); if (q[k] != cl[k]) outside = true; }
-    T dist;
-    if (outside) {
-      const T d[3] = {cl[0] - q[0], cl[1] - q[1], cl[2] - q[2]};
-      const T dn = t_sqrt(dot3(d, d));
-      dist = dn - r;
-      if (dist > margin) return 0;
-      for (int k = 0; k < 3; k++) nb[k] = d[k]/dn;
-    } else {
-      const T d0 = sb[0] - t_abs(cl[0]), d1 = sb[1] - t_abs(cl[1]), d2 = sb[2] - t_abs(cl[2]);
-      int best = 0; T depth = d0;
-      if (d1 < depth) { depth = d1; best = 1; }
-      if (d2 < depth) { depth = d2; best = 2; }
-      for (int k = 0; k < 3; k++) if (k == best) { nb[k] = cl[k] >= 0 ? (T)1 : (T)-1; q[k] = nb[k]*sb[k]; }
-      dist = -depth - r;
-    }
-    T nw[3], qw[3];
-    mul_mat_vec3(nw, mb, nb); mul_mat_vec3(qw, mb, q);
-    h->dist = dist;
-    for (int k = 0; k < 3; k++) { h->pos[k] = pb[k] + qw[k] + nw[k]*dist*(T)0.5; h->nrm[k] = -nw[k]; }
-    return 1;
-  }
-  DMC_DEV static T seg_box_dd(const T* p0, const T* u, const T* sb, T t, T* deriv) {
-    T f = 0, g = 0;
-    for (int k = 0; k < 3; k++) {
-      const T x = p0[k] + t*u[k], e = x - t_max(-sb[k], t_min(sb[k], x));
-      f += e*e; g += 2*e*u[k];
-    }
-    *deriv = g;
-    return f;
-  }
-  DMC_DEV static int capsule_box(Hits* hs, T margin, const T* p1, const T* m1, const T* s1, const T* p2, const T* m2, const T* s2) {
-    const T axw[3] = {m1[2], m1[5], m1[8]}, dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-    T p0[3], u[3];
-    mul_matT_vec3(p0, m2, dif); mul_matT_vec3(u, m2, axw);
-    const T hl = s1[1];
-    T lo = -hl, hi = hl, g, t;
-    seg_box_dd(p0, u, s2, lo, &g);
-    if (g >= 0) t = lo;
-    else {
-      seg_box_dd(p0, u, s2, hi, &g);
-      if (g <= 0) t = hi;
-      else {
-        for (int it = 0; it < (sizeof(T) == 8 ? 60 : 30); it++) { t = (T)0.5*(lo + hi); seg_box_dd(p0, u, s2, t, &g); if (g > 0) hi = t; else lo = t; }
-        t = (T)0.5*(lo + hi);
-      }
-    }
-    int mask = 0;
-    T ps[3];
-    for (int k = 0; k < 3; k++) ps[k] = p1[k] + axw[k]*t;
-    mask |= sphere_box_core(&hs->s0, margin, ps, s1[0], p2, m2, s2);
-    const T t2 = t <= 0 ? hl : -hl;
-    if (t_abs(t2 - t) > (T)1e-3*hl) {
-      for (int k = 0; k < 3; k++) ps[k] = p1[k] + axw[k]*t2;
-      Hit x;
-      if (sphere_box_core(&x, margin, ps, s1[0], p2, m2, s2)) { put_hit(hs, mask & 1, x); mask = (mask << 1) | 1; }
-    }
-    return mask;
-  }
-  DMC_DEV static int box_box(Hits* hs, T margin, const T* pA, const T* RA, const T* sA, const T* pB, const T* RB, const T* sB) {
-    const T d[3] = {pB[0] - pA[0], pB[1] - pA[1], pB[2] - pA[2]};
-    T colA[3][3], colB[3][3];
-    for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) { colA[i][k] = RA[3*k + i]; colB[i][k] = RB[3*k + i]; }
-    T best = (T)-1e30; int code = -1; T bestn[3] = {0, 0, 0};
-    for (int i = 0; i < 6; i++) {
-      T L[3];
-      for (int k = 0; k < 3; k++) L[k] = i < 3 ? colA[i % 3][k] : colB[i % 3][k];
-      T ra = 0, rb = 0;
-      for (int k = 0; k < 3; k++) { ra += sA[k]*t_abs(dot3(L, colA[k])); rb += sB[k]*t_abs(dot3(L, colB[k])); }
-      const T proj = dot3(L, d), sep = t_abs(proj) - ra - rb;
-      if (sep > margin) return 0;
-      if (sep > best) { best = sep; code = i; for (int k = 0; k < 3; k++) bestn[k] = proj >= 0 ? L[k] : -L[k]; }
-    }
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-      T L[3];
-      cross3(L, colA[i], colB[j]);
-      const T ln = t_sqrt(dot3(L, L));
-      if (ln < (T)1e-6) continue;
-      for (int k = 0; k < 3; k++) L[k] /= ln;
-      T ra = 0, rb = 0;
-      for (int k = 0; k < 3; k++) { ra += sA[k]*t_abs(dot3(L, colA[k])); rb += sB[k]*t_abs(dot3(L, colB[k])); }
-      const T proj = dot3(L, d), sep = t_abs(proj) - ra - rb;
-      if (sep > margin) return 0;
-      if (sep > 0 ? sep > best : sep*(T)1.05 > best) {
-        if (!(sep > 0) && !(best < 0)) continue;
-        best = sep; code = 6 + 3*i + j; for (int k = 0; k < 3; k++) bestn[k] = proj >= 0 ? L[k] : -L[k];
-      }
-    }
-    if (code >= 6) {
-      const int i = (code - 6)/3, j = (code - 6) % 3;
-      T pa[3] = {pA[0], pA[1], pA[2]}, pb[3] = {pB[0], pB[1], pB[2]};
-      for (int k = 0; k < 3; k++) if (k != i) { const T sg = dot3(bestn, colA[k]) > 0 ? (T)1 : (T)-1; for (int a = 0; a < 3; a++) pa[a] += sg*sA[k]*colA[k][a]; }
-      for (int k = 0; k < 3; k++) if (k != j) { const T sg = dot3(bestn, colB[k]) > 0 ? (T)-1 : (T)1; for (int a = 0; a < 3; a++) pb[a] += sg*sB[k]*colB[k][a]; }
-      T ua[3], ub[3];
-      for (int k = 0; k < 3; k++) { ua[k] = colA[i][k]; ub[k] = colB[j][k]; }
-      const T w[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
-      const T uaub = dot3(ua, ub), q1 = dot3(ua, w), q2 = -dot3(ub, w), den = 1 - uaub*uaub;
-      T alpha = 0, beta = 0;
-      if (den > (T)1e-12) { alpha = (q1 + uaub*q2)/den; beta = (uaub*q1 + q2)/den; }
-      alpha = t_max(-sA[i], t_min(sA[i], alpha)); beta = t_max(-sB[j], t_min(sB[j], beta));
-      hs->s0.dist = best;
-      for (int k = 0; k < 3; k++) { hs->s0.pos[k] = (T)0.5*((pa[k] + alpha*ua[k]) + (pb[k] + beta*ub[k])); hs->s0.nrm[k] = bestn[k]; }
-      return 1;
-    }
-    const bool refA = code < 3;
-    T pR[3], sR[3], pI[3], sI[3], cR[3][3], cI[3][3], nref[3];
-    for (int k = 0; k < 3; k++) {
-      pR[k] = refA ? pA[k] : pB[k]; sR[k] = refA ? sA[k] : sB[k]; pI[k] = refA ? pB[k] : pA[k]; sI[k] = refA ? sB[k] : sA[k];
-      nref[k] = refA ? bestn[k] : -bestn[k];
-      for (int a = 0; a < 3; a++) { cR[k][a] = refA ? colA[k][a] : colB[k][a]; cI[k][a] = refA ? colB[k][a] : colA[k][a]; }
-    }
-    const int ax = refA ? code : code - 3;
-    int inc = 0; T incdot = (T)1e30;
-    for (int k = 0; k < 3; k++) { const T dk = dot3(nref, cI[k]); if (-t_abs(dk) < incdot) { incdot = -t_abs(dk); inc = k; } }
-    const T incsign = dot3(nref, cI[inc]) > 0 ? (T)-1 : (T)1;
-    const int i1 = (inc + 1) % 3, i2 = (inc + 2) % 3, r1 = (ax + 1) % 3, r2 = (ax + 2) % 3;
-    // (a quad clipped by four half-planes has at most eight vertices: each clip of a convex polygon adds at most one.  The
-    // arrays are indexed at run time, i.e. they live in scratch memory: 2 x 8 x 3 reals, half of what 16 slots took; the
-    // guards below only matter if rounding ever made a clipped polygon non-convex)
-    T poly[8][3], tmp[8][3];
-    int np_ = 4;
-    for (int v = 0; v < 4; v++) {
-      const T a = (v == 0 || v == 3) ? (T)1 : (T)-1, b = v < 2 ? (T)1 : (T)-1;
-      T pt[3];
-      for (int k = 0; k < 3; k++) pt[k] = pI[k] + incsign*sI[inc]*cI[inc][k] + a*sI[i1]*cI[i1][k] + b*sI[i2]*cI[i2][k] - pR[k];
-      poly[v][0] = dot3(pt, cR[r1]); poly[v][1] = dot3(pt, cR[r2]); poly[v][2] = dot3(pt, nref) - sR[ax];
-    }
-    for (int side = 0; side < 4 && np_ > 0; side++) {
-      const int coord = side >> 1; const T sg = (side & 1) ? (T)-1 : (T)1, lim = coord ? sR[r2] : sR[r1];
-      int nn = 0;
-      for (int v = 0; v < np_; v++) {
-        const T* P = poly[v]; const T* Q = poly[(v + 1) % np_];
-        const T dp = lim - sg*P[coord], dq = lim - sg*Q[coord];
-        if (dp >= 0 && nn < 8) { tmp[nn][0] = P[0]; tmp[nn][1] = P[1]; tmp[nn][2] = P[2]; nn++; }
-        if ((dp >= 0) != (dq >= 0) && nn < 8) { const T f = dp/(dp - dq); for (int k = 0; k < 3; k++) tmp[nn][k] = P[k] + f*(Q[k] - P[k]); nn++; }
-      }
-      np_ = nn;
-      for (int v = 0; v < np_; v++) for (int k = 0; k < 3; k++) poly[v][k] = tmp[v][k];
-    }
-    int nk = 0;
-    for (int v = 0; v < np_; v++) if (poly[v][2] <= margin) { for (int k = 0; k < 3; k++) poly[nk][k] = poly[v][k]; nk++; }
-    if (!nk) return 0;
-    int pick[4] = {0, 0, 0, 0}, npick = 0;
-    if (nk <= 4) { for (int v = 0; v < nk; v++) pick[npick++] = v; }
-    else {
-      T cx = 0, cy = 0; int deep = 0;
-      for (int v = 0; v < nk; v++) { cx += poly[v][0]; cy += poly[v][1]; if (poly[v][2] < poly[deep][2]) deep = v; }
-      cx /= nk; cy /= nk;
-      const T PI = (T)3.14159265358979323846;
-      const T a0 = t_atan2(poly[deep][1] - cy, poly[deep][0] - cx);
-      int used = 1 << deep;
-      pick[npick++] = deep;
-      for (int q = 1; q < 4; q++) {
-        const T target = a0 + q*(PI/2);
-        int bv = -1; T bd = (T)1e30;
-        for (int v = 0; v < nk; v++) if (!((used >> v) & 1)) {
-          const T da = t_abs(t_fmod(t_atan2(poly[v][1] - cy, poly[v][0] - cx) - target + 5*PI, 2*PI) - PI);
-          if (da < bd) { bd = da; bv = v; }
-        }
-        pick[npick++] = bv; used |= 1 << bv;
-      }
-    }
-    for (int q = 0; q < npick; q++) {
-      const T* P = poly[pick[q]];
-      Hit x;
-      x.dist = P[2];
-      for (int k = 0; k < 3; k++) { x.pos[k] = pR[k] + P[0]*cR[r1][k] + P[1]*cR[r2][k] + (sR[ax] + (T)0.5*P[2])*nref[k]; x.nrm[k] = bestn[k]; }
-      put_hit(hs, q, x);
-    }
-    return (1 << npick) - 1;
-  }
+  using Hit = dmc::Hit<T>;
+  using Hits = dmc::Hits<T>;
   // narrow phase for one pair; returns the mask of valid slots of h[0..3]
   // (slot order = MuJoCo's contact order); tang = optional shared tangent
-  // ---- sphere / capsule against a cylinder (the oracle's point_cylinder / sphere_cylinder_core / collide_capsule_cylinder) ----
-  // closest point of the SOLID cylinder (centre p, unit axis a, radius R, half-height H) to q; returns the distance
-  DMC_DEV static T point_cylinder(const T* q, const T* p, const T* a, T R, T H, T* closest) {
-    const T v[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
-    const T x = dot3(v, a), perp[3] = {v[0] - x*a[0], v[1] - x*a[1], v[2] - x*a[2]};
-    const T d = t_sqrt(dot3(perp, perp)), xc = t_max(-H, t_min(H, x)), sc = d > R ? R/d : (T)1;
-    for (int k = 0; k < 3; k++) closest[k] = p[k] + xc*a[k] + sc*perp[k];
-    const T dif[3] = {q[0] - closest[0], q[1] - closest[1], q[2] - closest[2]};
-    return t_sqrt(dot3(dif, dif));
-  }
-  DMC_DEV static int sphere_cylinder_core(Hit* hit, T margin, const T* ps, T rs, const T* p2, const T* m2, const T* s2) {
-    const T a[3] = {m2[2], m2[5], m2[8]}, R = s2[0], H = s2[1];
-    T closest[3], n[3], dist;
-    const T g = point_cylinder(ps, p2, a, R, H, closest);
-    if (g >= (T)DMC_MINVAL) {
-      dist = g - rs;
-      for (int k = 0; k < 3; k++) n[k] = (closest[k] - ps[k]) / g;
-    } else {      // centre inside the solid: out through the nearest face
-      const T v[3] = {ps[0] - p2[0], ps[1] - p2[1], ps[2] - p2[2]};
-      const T x = dot3(v, a), perp[3] = {v[0] - x*a[0], v[1] - x*a[1], v[2] - x*a[2]}, d = t_sqrt(dot3(perp, perp));
-      if (H - t_abs(x) < R - d) { dist = -(H - t_abs(x)) - rs; for (int k = 0; k < 3; k++) n[k] = x >= 0 ? -a[k] : a[k]; }
-      else {
-        dist = -(R - d) - rs;
-        if (d < (T)DMC_MINVAL) { n[0] = 1; n[1] = n[2] = 0; } else for (int k = 0; k < 3; k++) n[k] = -perp[k] / d;
-      }
-    }
-    if (dist > margin) return 0;
-    hit->dist = dist;
-    for (int k = 0; k < 3; k++) { hit->pos[k] = ps[k] + n[k]*(rs + dist*(T)0.5); hit->nrm[k] = n[k]; }
-    return 1;
-  }
-  // slope of the point-to-cylinder distance along the capsule axis at p1 + t u (nondecreasing in t)
-  DMC_DEV static T segment_slope(T t, const T* p1, const T* u, const T* p2, const T* a, T R, T H) {
-    const T q[3] = {p1[0] + t*u[0], p1[1] + t*u[1], p1[2] + t*u[2]};
-    T closest[3];
-    const T g = point_cylinder(q, p2, a, R, H, closest);
-    if (g < (T)DMC_MINVAL) return 0;
-    return ((q[0] - closest[0])*u[0] + (q[1] - closest[1])*u[1] + (q[2] - closest[2])*u[2]) / g;
-  }
-  DMC_DEV static T slope_crossing(T thr, T h, const T* p1, const T* u, const T* p2, const T* a, T R, T H) {
-    if (segment_slope(-h, p1, u, p2, a, R, H) > thr) return -h;
-    if (!(segment_slope(h, p1, u, p2, a, R, H) > thr)) return h;
-    T lo = -h, hi = h;
-    for (int it = 0; it < (sizeof(T) == 4 ? 28 : 60); it++) {
-      const T t = (T)0.5*(lo + hi);
-      if (segment_slope(t, p1, u, p2, a, R, H) > thr) hi = t; else lo = t;
-    }
-    return (T)0.5*(lo + hi);
-  }
-  // returns 0 / 1 contacts, or -1 when the capsule's axis reaches the cylinder (no unique closest pair: the caller warns)
-  DMC_DEV static int capsule_cylinder(Hit* hit, T margin, const T* p1, const T* m1, const T* s1, const T* p2, const T* m2, const T* s2) {
-    const T u[3] = {m1[2], m1[5], m1[8]}, a[3] = {m2[2], m2[5], m2[8]};
-    const T tol = sizeof(T) == 4 ? (T)1e-4 : (T)1e-7;
-    const T ta = slope_crossing(-tol, s1[1], p1, u, p2, a, s2[0], s2[1]);
-    const T tb = slope_crossing(tol, s1[1], p1, u, p2, a, s2[0], s2[1]);
-    const T t = (T)0.5*(ta + tb);
-    const T q[3] = {p1[0] + t*u[0], p1[1] + t*u[1], p1[2] + t*u[2]};
-    T closest[3];
-    if (point_cylinder(q, p2, a, s2[0], s2[1], closest) < (sizeof(T) == 4 ? (T)1e-5 : (T)1e-9)*(s2[0] + s2[1])) return -1;
-    return sphere_cylinder_core(hit, margin, q, s1[0], p2, m2, s2);
-  }
   DMC_DEV int narrow_phase(int g1, int g2, T margin, Hits* h, T* tang, bool* has_tang, bool* guard) {
     int t1 = MI(geom_type)[g1], t2 = MI(geom_type)[g2];
     // cylinders: against a plane, a sphere or a capsule the narrow phase is restated; every other pair is tested as the
@@ -3157,113 +2053,6 @@ struct StepCore {
       }
       DMC_WSYNC();
     }
-  }
-  // ray (pnt, vec) against a site volume in its own frame; distance or -1
-  DMC_DEV static T ray_geom(const T* pos, const T* mat, const T* size, const T* pnt, const T* vec, int type) {
-    T dif[3] = {pnt[0] - pos[0], pnt[1] - pos[1], pnt[2] - pos[2]}, lp[3], lv[3];
-    mul_matT_vec3(lp, mat, dif); mul_matT_vec3(lv, mat, vec);
-    T best = -1;
-    if (type == DMC_GEOM_SPHERE || type == DMC_GEOM_CAPSULE) {
-      const T r = size[0];
-      const int nparts = type == DMC_GEOM_CAPSULE ? 3 : 1;
-      for (int part = 0; part < nparts; part++) {
-        T a, b, c;
-        if (type == DMC_GEOM_CAPSULE && part == 0) {
-          a = lv[0]*lv[0] + lv[1]*lv[1]; b = lp[0]*lv[0] + lp[1]*lv[1]; c = lp[0]*lp[0] + lp[1]*lp[1] - r*r;
-        } else {
-          const T cz = type == DMC_GEOM_CAPSULE ? (part == 1 ? size[1] : -size[1]) : (T)0;
-          T q[3] = {lp[0], lp[1], lp[2] - cz};
-          a = dot3(lv, lv); b = dot3(q, lv); c = dot3(q, q) - r*r;
-        }
-        if (a < (T)DMC_MINVAL) continue;
-        const T det = b*b - a*c;
-        if (det < 0) continue;
-        const T sq = t_sqrt(det);
-        for (int k = 0; k < 2; k++) {
-          const T x = k == 0 ? (-b - sq)/a : (-b + sq)/a;
-          if (x < 0) continue;
-          const T z = lp[2] + x*lv[2];
-          if (type == DMC_GEOM_CAPSULE) {
-            if (part == 0 && t_abs(z) > size[1]) continue;
-            if (part == 1 && z < size[1]) continue;
-            if (part == 2 && z > -size[1]) continue;
-          }
-          if (best < 0 || x < best) best = x;
-        }
-      }
-      return best;
-    }
-    if (type == DMC_GEOM_ELLIPSOID) {
-      T q[3] = {lp[0]/size[0], lp[1]/size[1], lp[2]/size[2]}, w[3] = {lv[0]/size[0], lv[1]/size[1], lv[2]/size[2]};
-      const T a = dot3(w, w), b = dot3(q, w), c = dot3(q, q) - 1;
-      if (a < (T)DMC_MINVAL) return -1;
-      const T det = b*b - a*c;
-      if (det < 0) return -1;
-      const T sq = t_sqrt(det), x0 = (-b - sq)/a, x1 = (-b + sq)/a;
-      return x0 >= 0 ? x0 : (x1 >= 0 ? x1 : (T)-1);
-    }
-    if (type == DMC_GEOM_BOX) {
-      if (t_abs(lp[0]) <= size[0] && t_abs(lp[1]) <= size[1] && t_abs(lp[2]) <= size[2]) return 0;
-      for (int ax = 0; ax < 3; ax++) {
-        if (t_abs(lv[ax]) < (T)DMC_MINVAL) continue;
-        for (int sg = -1; sg <= 1; sg += 2) {
-          const T x = (sg*size[ax] - lp[ax]) / lv[ax];
-          if (x < 0) continue;
-          const int a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
-          if (t_abs(lp[a1] + x*lv[a1]) <= size[a1] && t_abs(lp[a2] + x*lv[a2]) <= size[a2])
-            if (best < 0 || x < best) best = x;
-        }
-      }
-      return best;
-    }
-    return -1;
-  }
-  // rays of rangefinder sensors: every geom type (planes are front-side only and finite where their
-  // half-sizes are positive; a ray that starts inside a box leaves through a face)
-  DMC_DEV static T ray_geom_any(const T* pos, const T* mat, const T* size, const T* pnt, const T* vec, int type) {
-    if (type != DMC_GEOM_PLANE && type != DMC_GEOM_CYLINDER && type != DMC_GEOM_BOX) return ray_geom(pos, mat, size, pnt, vec, type);
-    T dif[3] = {pnt[0] - pos[0], pnt[1] - pos[1], pnt[2] - pos[2]}, lp[3], lv[3];
-    mul_matT_vec3(lp, mat, dif); mul_matT_vec3(lv, mat, vec);
-    T best = -1;
-    if (type == DMC_GEOM_PLANE) {
-      if (lv[2] > -(T)DMC_MINVAL) return -1;
-      const T x = -lp[2]/lv[2];
-      if (x < 0) return -1;
-      const T px = lp[0] + x*lv[0], py = lp[1] + x*lv[1];
-      if ((size[0] <= 0 || t_abs(px) <= size[0]) && (size[1] <= 0 || t_abs(py) <= size[1])) return x;
-      return -1;
-    }
-    if (type == DMC_GEOM_CYLINDER) {
-      const T a = lv[0]*lv[0] + lv[1]*lv[1], b = lp[0]*lv[0] + lp[1]*lv[1], c = lp[0]*lp[0] + lp[1]*lp[1] - size[0]*size[0];
-      if (a >= (T)DMC_MINVAL) {
-        const T det = b*b - a*c;
-        if (det >= 0) {
-          const T sq = t_sqrt(det);
-          for (int k = 0; k < 2; k++) {
-            const T x = k == 0 ? (-b - sq)/a : (-b + sq)/a;
-            if (x >= 0 && t_abs(lp[2] + x*lv[2]) <= size[1]) if (best < 0 || x < best) best = x;
-          }
-        }
-      }
-      if (t_abs(lv[2]) >= (T)DMC_MINVAL) for (int sg = -1; sg <= 1; sg += 2) {
-        const T x = (sg*size[1] - lp[2]) / lv[2];
-        if (x < 0) continue;
-        const T px = lp[0] + x*lv[0], py = lp[1] + x*lv[1];
-        if (px*px + py*py <= size[0]*size[0]) if (best < 0 || x < best) best = x;
-      }
-      return best;
-    }
-    for (int ax = 0; ax < 3; ax++) {
-      if (t_abs(lv[ax]) < (T)DMC_MINVAL) continue;
-      for (int sg = -1; sg <= 1; sg += 2) {
-        const T x = (sg*size[ax] - lp[ax]) / lv[ax];
-        if (x < 0) continue;
-        const int a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
-        if (t_abs(lp[a1] + x*lv[a1]) <= size[a1] && t_abs(lp[a2] + x*lv[a2]) <= size[a2])
-          if (best < 0 || x < best) best = x;
-      }
-    }
-    return best;
   }
   DMC_DEV void sensors_acc() {
     if ((o.disableflags & DMC_DSBL_SENSOR) || L.d.nsensor == 0) return;
@@ -4611,11 +3400,7 @@ struct StepCore {
     // pivot serves both L[i][i] and every division by it (the exact form costs ~10 correctly rounded divisions /
     // roots per trip), and the stopping tests are floored at what fp32 resolves (|v|^2 - r^2 cannot get within
     // 1e-10 of zero when r^2 ~ 1e4); fp64 keeps MuJoCo's sequence operation for operation.
-#ifdef DMC_EXACT_QCQP
-    constexpr bool fast = false;
-#else
     constexpr bool fast = sizeof(T) == 4;
-#endif
     T A[N*N], b[N], Lc[N*N], inv[N], v[N], pv[N], la = 0;
 #pragma unroll
     for (int i = 0; i < N; i++) { v[i] = 0; pv[i] = 0; inv[i] = 0; b[i] = bin[i]*dd[i]; }
@@ -4868,11 +3653,7 @@ struct StepCore {
   // once.  fp64 re-solves them every sweep, operation for operation as the oracle does (noslip_tolerance = 0 models run
   // all their sweeps).
   DMC_DEV T noslip_sweep_levels(int nf, int nb, int nlev, bool first) {
-#if defined(DMC_EXACT_QCQP) || defined(DMC_NS_RESWEEP_ALL)
-    constexpr bool once = false;
-#else
     constexpr bool once = sizeof(T) == 4;
-#endif
     for (int lev = 1; lev <= nlev; lev++) {
       FOR_LANES(k, nb) {
         const int d = SI(ns_blk)[k];
@@ -5056,7 +3837,7 @@ struct StepCore {
   DMC_DEV void noslip(int nefc) {
     const int nv = L.d.nv, cap = L.d.nslip;
     int nf = 0, over = 0;
-#if defined(DMC_HOST_EMU) || defined(DMC_NS_SCAN_SERIAL)
+#ifdef DMC_HOST_EMU
     for (int i = 0; i < nefc; i++) {
       const int tid = SI(efc_tid)[i], t = EFC_TYPE(tid);
       bool take = t == EFC_FRICTION || t == EFC_PYRAMIDAL;
@@ -5142,12 +3923,10 @@ struct StepCore {
 #endif
       iter++;
       if (improvement < o.noslip_tolerance) break;
-#if !defined(DMC_EXACT_QCQP) && !defined(DMC_NS_RESWEEP_ALL)
       // fp32 solves a block without a partner once (noslip_sweep_levels): when NO block has one -- one level: every
       // contact on a tree of its own, the usual state of the soccer pitch -- the later sweeps would skip every block and
       // add up zeros (noslip_tolerance = 0 never ends them: 0 < 0), so the pass ends here with the same forces
       if (sizeof(T) == 4 && nblk && nlev == 1) break;
-#endif
     }
 #ifdef DMC_HOST_EMU
     emu_ls_counts()[2]++; emu_ls_counts()[3] += iter;

@@ -4,10 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef DMC_STEP_CORE_HEADER   // tuning studies build variants of the core from other files
-#define DMC_STEP_CORE_HEADER "step_core.h"
-#endif
-#include DMC_STEP_CORE_HEADER
+#include "step_core.h"
 #ifdef DMC_TASK_HEADER      // (a specialisation plugin with a task epilogue: dm_control_amd/suite/fused_env.py)
 #define DMC_TASK_IN_KERNEL 1
 #include DMC_TASK_HEADER

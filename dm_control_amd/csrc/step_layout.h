@@ -13,10 +13,7 @@
 #include <stdint.h>
 
 // StepDims::jglobal of a model with nv dofs
-#ifndef DMC_JGLOBAL_NV1
-#define DMC_JGLOBAL_NV1 16      // (experiment knob: dofs from which level 1 applies)
-#endif
-#define DMC_JGLOBAL_LEVEL(nv) ((nv) > 48 ? 3 : ((nv) > 32 ? 2 : ((nv) > DMC_JGLOBAL_NV1 ? 1 : 0)))
+#define DMC_JGLOBAL_LEVEL(nv) ((nv) > 48 ? 3 : ((nv) > 32 ? 2 : ((nv) > 16 ? 1 : 0)))
 
 struct StepDims {
   int nq, nv, nu, nbody, njnt, ngeom, nsite, nsensor, nsensordata, npair;

@@ -41,8 +41,7 @@ from dm_control_amd import build as _build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-_SOURCES = ('step_core.h', 'step_layout.h', 'step_tables.h', 'step_kernel.hip.h', 'step_kernel_spec.hip',
-            '../../include/dmc_model_layout.h', '../../include/dmc_batch.h')
+_SOURCES = _build.STEP_SOURCES + ('step_kernel_spec.hip',)
 _source_hash = None
 
 

@@ -2,7 +2,7 @@
 
 62 degrees of freedom, 56 motors, capsule limbs, sphere toes and two ellipsoid hands that collide with
 the whole body (1118 candidate pairs): the ellipsoid pairs use the iterative support-function narrow
-phase (csrc/step_core.h `ellipsoid_pair`).  The task is the suite humanoid's with the thorax as torso
+phase (csrc/step_geom.h `ellipsoid_pair`).  The task is the suite humanoid's with the thorax as torso
 (uprightness = thorax y axis on world z) and `l` / `r` limb prefixes, so it is built from that
 module's classes."""
 from dm_control_amd.envs import control

@@ -1,5 +1,5 @@
 // Probe and device test (VERDICT r05 #1a): the fp32 Cholesky factorisation of the Newton Hessian of a 33 .. 64-dof model, one
-// wave per matrix, on the packed lower triangle in LDS -- the two PRODUCTION routines of dm_control_amd/csrc/step_core.h:
+// wave per matrix, on the packed lower triangle in LDS -- the two PRODUCTION routines of dm_control_amd/csrc/step_dense.h:
 //   rows  : chol_factor_rows<N>: lane i keeps row i in N registers, pivots and scaled columns travel by v_readlane
 //           (2 instructions per updated entry, N (N - 1) of them)
 //   tiles : chol_factor_tiles<N>: blocked right-looking U'U on 16 x 16 tiles in the matrix cores' accumulator layout; a tile
@@ -13,7 +13,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
-#include "../dm_control_amd/csrc/step_core.h"
+#include "../dm_control_amd/csrc/step_dense.h"
 
 #define LDS __attribute__((address_space(3)))
 

@@ -1,15 +1,19 @@
-"""ISA of one code object attributed to source functions of step_core.h (build the plugin with -gline-tables-only):
+"""ISA of one code object attributed to source functions of the step core's headers (csrc/step_*.h; build the plugin with -gline-tables-only):
    python scripts/isa_by_source.py <plugin.so> <stage: posvel|acc|euler|kernel> [function ...]     -- listing of those functions' instructions
    without function names: static instruction counts per source function."""
 import bisect, collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = open(os.path.join(ROOT, 'dm_control_amd/csrc/step_core.h')).read().splitlines()
-starts, names = [], []
-for i, l in enumerate(src, 1):
-  m = re.match(r'\s*(?:template <[^>]*>\s*)?(?:static )?(?:DMC_DEV|DMC_FN)\s+(?:static\s+)?[\w:<>\*& ,\(\)]*?\b(\w+)\s*\(', l)
-  if m and not l.strip().startswith('//'):
-    starts.append(i); names.append(m.group(1))
-def fn(line):
+CSRC = os.path.join(ROOT, 'dm_control_amd/csrc')
+index = {}      # header -> (first lines of its functions, their names)
+for h in sorted(os.listdir(CSRC)):
+  if not (h.startswith('step_') and h.endswith('.h')): continue
+  starts, names = index.setdefault(h, ([], []))
+  for i, l in enumerate(open(os.path.join(CSRC, h)).read().splitlines(), 1):
+    m = re.match(r'\s*(?:template <[^>]*>\s*)?(?:static )?(?:DMC_DEV|DMC_FN)\s+(?:static\s+)?[\w:<>\*& ,\(\)]*?\b(\w+)\s*\(', l)
+    if m and not l.strip().startswith('//'):
+      starts.append(i); names.append(m.group(1))
+def fn(header, line):
+  starts, names = index[header]
   k = bisect.bisect_right(starts, line) - 1
   return names[k] if k >= 0 else '?'
 blob = open(sys.argv[1], 'rb').read()
@@ -32,7 +36,7 @@ for l in out:
   if m:
     cur = (m.group(1).split('/')[-1], int(m.group(2))); continue
   if l.startswith('\t') and func == stage and cur:
-    key = fn(cur[1]) if cur[0] == 'step_core.h' else cur[0]
+    key = fn(*cur) if cur[0] in index else cur[0]
     cnt[key] += 1
     rows.append((cur[1], key, re.sub(r'\s*//.*', '', l.strip())[:110]))
     if key in want:

@@ -1,6 +1,6 @@
-// Device unit test of the CROSS-LANE layer of dm_control_amd/csrc/step_core.h, in isolation from the step kernel: the
+// Device unit test of the CROSS-LANE layer of dm_control_amd/csrc/step_lanes.h, in isolation from the step kernel: the
 // reductions / broadcasts / scans (DPP quad_perm / row_mirror / row_shr / row_newbcast / row_bcast, v_permlane16/32_swap,
-// v_readlane) for 16, 32 and 64 lanes per environment, and the row-per-lane linear algebra built on them
+// v_readlane) for 16, 32 and 64 lanes per environment, and the row-per-lane linear algebra built on them in step_dense.h
 // (chol_factor_rows / chol_solve_rows, the per-tree chol_factor_trees / chol_solve_trees) against host references and
 // against the fenced LDS forms (chol_factor_lds / chol_solve_lds) they replaced.  None of this is reachable on the CPU
 // tier: tests/emu runs the kernel core with one lane per environment, where every one of these is the identity.
@@ -12,7 +12,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "../dm_control_amd/csrc/step_core.h"
+#include "../dm_control_amd/csrc/step_lanes.h"
+#include "../dm_control_amd/csrc/step_dense.h"
 
 #define LDS __attribute__((address_space(3)))
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(2); } } while (0)

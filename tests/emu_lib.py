@@ -21,8 +21,8 @@ IFIELDS = ['ncon', 'nefc', 'solver_iter', 'warning', 'contact_geom1', 'contact_g
 def lib():
   global _lib
   if _lib is None:
-    csrc = os.path.join(os.path.dirname(_HERE), 'dm_control_amd', 'csrc')
-    deps = [_SRC] + [os.path.join(csrc, f) for f in ('step_core.h', 'step_layout.h', 'step_tables.h')]
+    from dm_control_amd import build
+    deps = [_SRC] + [os.path.join(build.CSRC, f) for f in build.STEP_SOURCES]
     stale = lambda: not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in deps)
     if stale():
       # (pytest-xdist workers may all find it stale at once: one builds under a lock, into a temporary that is moved in

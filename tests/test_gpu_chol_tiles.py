@@ -1,4 +1,4 @@
-"""chol_factor_tiles (step_core.h: the fp32 Newton Hessian of a 33 .. 64-dof model factored on the matrix cores) against an
+"""chol_factor_tiles (step_dense.h: the fp32 Newton Hessian of a 33 .. 64-dof model factored on the matrix cores) against an
 fp64 factor of the same matrices and against chol_factor_rows, for matrix sizes on both sides of every tile boundary --
 the production routines, compiled into scripts/chol_mfma_probe.hip.  The step kernels that use the routine are compared
 with the oracle in test_gpu_suite.py (configs 4 / 5); this is the routine alone, including what it writes past the

@@ -1,4 +1,4 @@
-"""The cross-lane layer of step_core.h on the device, in isolation (scripts/lane_primitives_probe.hip builds the production
+"""The cross-lane layer of step_lanes.h on the device, in isolation (scripts/lane_primitives_probe.hip builds the production
 routines): group_sum / group_max / group_scan / wave_bcast / the row_newbcast form of bcast_rows for 16, 32 and 64 lanes per
 environment against host sums, maxima, prefix sums and lane picks (exact: the inputs make every partial sum exact); the
 row-per-lane Cholesky factorisation and substitution (v_readlane / DPP broadcasts, several environments per wave) against an

@@ -1,4 +1,4 @@
-"""Factorisations block diagonal over the kinematic trees (StepDims::treemax, step_core.h chol_factor_trees /
+"""Factorisations block diagonal over the kinematic trees (StepDims::treemax, step_dense.h chol_factor_trees /
 chol_solve_trees / hess_assemble_split / h_split).
 
 CPU tier: the tables, and the emulated kernel core, which under DMC_HOST_EMU checks on EVERY split solve that the full
