@@ -32,11 +32,21 @@ def _load():
   hdr_reals = re.findall(r'X\((\w+)\)', _macro_body(text, 'DMC_MODEL_HEADER_REALS'))
   int_fields = re.findall(r'X\((\w+),\s*([^)]+)\)', _macro_body(text, 'DMC_MODEL_INT_FIELDS'))
   real_fields = re.findall(r'X\((\w+),\s*([^)]+)\)', _macro_body(text, 'DMC_MODEL_REAL_FIELDS'))
-  return consts, hdr_ints, hdr_reals, int_fields, real_fields
+  # the batch's data fields, X(name, count_expr, flags): (name, count_expr) pairs like the model's
+  data_real, data_int = [[m[:2] for m in re.findall(r'X\((\w+),\s*([^,)]+),\s*([^)]+)\)', _macro_body(text, 'DMC_DATA_%s_FIELDS' % k))]
+                         for k in ('REAL', 'INT')]
+  return consts, hdr_ints, hdr_reals, int_fields, real_fields, data_real, data_int
 
 
-CONSTS, HEADER_INTS, HEADER_REALS, INT_FIELDS, REAL_FIELDS = _load()
+CONSTS, HEADER_INTS, HEADER_REALS, INT_FIELDS, REAL_FIELDS, DATA_REAL_FIELDS, DATA_INT_FIELDS = _load()
 
 
 def field_count(expr, sizes):
   return int(eval(expr, {}, dict(sizes)))  # count expressions are e.g. "3*nbody"
+
+
+def data_field_counts(model, nconmax):
+  """Rows per environment of every data field (DATA_REAL_FIELDS + DATA_INT_FIELDS) for a compiled model and a contact cap."""
+  sizes = dict(CONSTS, nconmax=nconmax, **{k: getattr(model, k) for k in
+                                          ('nq', 'nv', 'nu', 'na', 'nbody', 'ngeom', 'nsite', 'nsensordata', 'nmocap')})
+  return {n: field_count(e, sizes) for n, e in DATA_REAL_FIELDS + DATA_INT_FIELDS}

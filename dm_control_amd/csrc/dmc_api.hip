@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -37,58 +37,102 @@ struct dmc_model {
   HostModel hm;
 };
 
+// The batch's data fields: one id per entry of DMC_DATA_REAL_FIELDS / DMC_DATA_INT_FIELDS (dmc_model_layout.h), in that
+// order, and one reserved slot for the per-environment geoms, which exist once dmc_batch_set_env_geoms declared them.
+enum FieldId {
+#define X(name, count, flags) F_##name,
+  DMC_DATA_REAL_FIELDS(X) DMC_DATA_INT_FIELDS(X)
+#undef X
+  F_env_geom, F_COUNT
+};
 struct Field {
-  std::string name;
-  int rows;
-  bool is_int;
-  bool is_f64;     // stored as double regardless of the batch precision (time)
-  void* dev;       // current binding
-  void* owned;     // hipMalloc'ed by us (may differ from dev after dmc_batch_bind)
+  const char* name = nullptr;      // null: not declared (F_env_geom)
+  int rows = 0;
+  bool is_int = false;
+  int flags = 0;             // DMC_FIELD_*
+  void* dev = nullptr;       // current binding
+  void* owned = nullptr;     // allocated by us (may differ from dev after dmc_batch_bind)
+};
+
+struct TimerPair { hipEvent_t e0, e1; int which, count; };
+struct Profiler {
+  bool on = false;
+  double duration[2] = {0, 0};      // seconds: [mjTIMER_STEP, mjTIMER_FORWARD]
+  long long number[2] = {0, 0};
+  std::vector<TimerPair> pending, spare;
+};
+struct Xfer {
+  static constexpr int kSlots = 4;
+  void* h_in[kSlots] = {}; void* d_in[kSlots] = {}; size_t cap_in[kSlots] = {}; hipEvent_t ev_in[kSlots] = {}; int next = 0;
+  void* h_out = nullptr; void* d_out = nullptr; size_t cap_out = 0; hipEvent_t ev_out = nullptr;
+  std::vector<std::pair<Field*, size_t>> pending;      // fields of the enqueued get and their offsets (elements) in the staging
+  bool out_in_flight = false;
 };
 
 struct dmc_batch {
-  const dmc_model* model;
-  int B, device, precision;
+  const dmc_model* model = nullptr;
+  int B = 0, device = 0, precision = 0;
   StepTables tb;
   LaunchGeom geom;
-  int* d_mi;
-  int* d_mc;      // cold int tables (stay in global memory)
-  void* d_mr;
-  StepLayout* d_layout;
-  std::vector<Field> fields;
-  std::map<std::string, int> index;
-  int outmask;
+  std::vector<void*> dev_bufs;      // every device allocation of the batch (dev_alloc), freed by dmc_batch_destroy
+  int* d_mi = nullptr;
+  int* d_mc = nullptr;      // cold int tables (stay in global memory)
+  void* d_mr = nullptr;
+  StepLayout* d_layout = nullptr;
+  Field fields[F_COUNT];      // fixed: a Field* stays valid for the life of the batch
+  int outmask = OUT_ALL;
   int launched_mask = 0;      // the output mask the last step / forward launch ran with (what the derived arrays in HBM hold)
-  int ndebug;
-  void* d_debug;
-  int* d_debug_i;
-  long long* d_prof;
-  size_t elem;  // sizeof(T)
+  int ndebug = 0;
+  void* d_debug = nullptr;
+  int* d_debug_i = nullptr;
+  long long* d_prof = nullptr;
+  size_t elem = 0;  // sizeof(T)
   // per-env stash of the position / velocity stage between legacy steps (StepIO::stash_*); epoch: bumped by every
   // host-side edit that can change what the stage depends on, which invalidates all stashes at once
-  void* d_stash_r; int* d_stash_i; int* d_epoch; int stash_on; int stash_auto;
-  int xfrc_on;         // xfrc_applied was written / bound / exposed: the kernel reads it from now on
-  void* d_ns_A;        // noslip: (B, nslip, nslip) reals in global memory (StepOpts::ns_A)
-  int* d_work;         // work queue of launches with a resident-only grid: {next item, finished waves} (StepIO::work)
-  int ncu;             // compute units of the device
-  void* d_kstash; int* d_kstash_i;      // kinematic stash (StepIO::kstash), on unless DMC_NO_KSTASH
-  int *d_cost, *d_order; int lpt, nitems;      // longest-first scheduling of queued launches (StepIO::cost / order)
+  void* d_stash_r = nullptr; int* d_stash_i = nullptr; int* d_epoch = nullptr; int stash_on = 0; int stash_auto = 0;
+  int xfrc_on = 0;               // xfrc_applied was written / bound / exposed: the kernel reads it from now on
+  void* d_ns_A = nullptr;        // noslip: (B, nslip, nslip) reals in global memory (StepOpts::ns_A)
+  int* d_work = nullptr;         // work queue of launches with a resident-only grid: {next item, finished waves} (StepIO::work)
+  int ncu = 0;                   // compute units of the device
+  void* d_kstash = nullptr; int* d_kstash_i = nullptr;      // kinematic stash (StepIO::kstash), on unless DMC_NO_KSTASH
+  int *d_cost = nullptr, *d_order = nullptr; int lpt = 0, nitems = 0;      // longest-first scheduling of queued launches (StepIO::cost / order)
   int* d_prog = nullptr; int max_slices = 0;   // sliced items of queued multi-step launches (StepIO::prog / slices)
   unsigned long long* d_hand = nullptr; int hand_n = 0; int nxcd = 1;      // hand-off records of the pieces; queues per launch (one per XCD)
-  void* d_gscr;        // large models: (B, n_gs) reals of per-env global scratch (StepOpts::gscr)
-  int* d_trace;        // wave trace (dmc_batch_wave_trace): ring of 8 launches x (8, nitems) ints, or null
-  struct Profiler* prof = nullptr;      // launch timers (dmc_batch_enable_profiling), or null
-  struct Xfer* xfer = nullptr;      // pinned / device staging of the asynchronous host transfers (dmc_batch_set_async / get_async), or null
+  void* d_gscr = nullptr;        // large models: (B, n_gs) reals of per-env global scratch (StepOpts::gscr)
+  int* d_trace = nullptr;        // wave trace (dmc_batch_wave_trace): ring of 8 launches x (8, nitems) ints, or null
+  Profiler* prof = nullptr;      // launch timers (dmc_batch_enable_profiling), or null
+  Xfer* xfer = nullptr;      // pinned / device staging of the asynchronous host transfers (dmc_batch_set_async / get_async), or null
   void* d_probe = nullptr; int probe_geom = 0, probe_cap = 0;      // substep probe (dmc_batch_set_step_probe): caller-owned (cap, 3, B) reals
-  int trace_launch;    // launches since the trace was switched on (ring slot = trace_launch % 8)
-  int* d_rj_i; double* d_rj_r;      // joint randomisation: (4, njnt) ints {type, qposadr, limited, 0} and (2, njnt) ranges
-  int* d_eg_slot;      // per-env world geoms: (ngeom) slot table on the device (field "env_geom" holds the values)
+  int trace_launch = 0;    // launches since the trace was switched on (ring slot = trace_launch % 8)
+  int* d_rj_i = nullptr; double* d_rj_r = nullptr;      // joint randomisation: (4, njnt) ints {type, qposadr, limited, 0} and (2, njnt) ranges
+  int* d_eg_slot = nullptr;      // per-env world geoms: (ngeom) slot table on the device (field F_env_geom holds the values)
   // a model-specialised kernel built on demand for this model (dmc_batch_attach_specialised): the loaded object, its launch
   // entry, whether it holds the optional launch features (step_core.h kFeat)
   void* spec_so = nullptr; void* spec_launch = nullptr; int spec_features = 0;
   int spec_task_bytes = 0;      // > 0: the attached kernel carries a task epilogue with an argument block of this size
   void* d_task_args = nullptr; int task_on = 0;      // its arguments on the device; whether the next step launches run it
 };
+
+// Device memory of a batch: allocate, optionally zero or fill from `init`, record; a failure leaves *ptr null and the
+// error "hipMalloc <what>: <hip error>".  dmc_batch_destroy frees what is recorded; dev_free releases one buffer early.
+template <typename P>
+static int dev_alloc(dmc_batch* b, P** ptr, size_t bytes, bool zero, const char* what, const void* init = nullptr) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e == hipSuccess && zero) e = hipMemset(p, 0, bytes);
+  if (e == hipSuccess && init) e = hipMemcpy(p, init, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { if (p) (void)hipFree(p); return fail(std::string("hipMalloc") + (*what ? " " : "") + what + ": " + hipGetErrorString(e), -2); }
+  b->dev_bufs.push_back(p);
+  *ptr = (P*)p;
+  return 0;
+}
+template <typename P>
+static void dev_free(dmc_batch* b, P** ptr) {
+  if (!*ptr) return;
+  b->dev_bufs.erase(std::find(b->dev_bufs.begin(), b->dev_bufs.end(), (void*)*ptr));
+  (void)hipFree(*ptr);
+  *ptr = nullptr;
+}
 
 extern "C" const char* dmc_last_error(void) { return g_err.c_str(); }
 
@@ -102,9 +146,57 @@ extern "C" int dmc_model_create(const int32_t* ints, int n_ints, const double* r
 }
 extern "C" void dmc_model_destroy(dmc_model* m) { delete m; }
 
+// (only where a caller passes a name: everything inside the library addresses fields by id)
 static Field* find_field(dmc_batch* b, const char* name) {
-  auto it = b->index.find(name);
-  return it == b->index.end() ? nullptr : &b->fields[it->second];
+  if (name) for (Field& f : b->fields) if (f.name && !strcmp(f.name, name)) return &f;
+  return nullptr;
+}
+
+// ---- profiling contract (mujoco/engine.py:135-137 enable_profiling -> wrapper.enable_timer; mjData.timer[]) ------
+// MuJoCo brackets mj_step / mj_forward with the mjcb_time callback and accumulates duration and call count per timer.
+// Here a launch IS the step: with profiling enabled every launch is bracketed by two hipEvents on its stream; the pairs
+// are resolved lazily (completed ones whenever a new launch is issued, all of them when the timer is read), so an
+// asynchronous caller is not serialised.  Launches recorded into a HIP graph are not timed (events cannot be queried
+// across replays).
+static void prof_drain(Profiler* p, bool all) {
+  size_t k = 0;
+  for (; k < p->pending.size(); k++) {
+    TimerPair& t = p->pending[k];
+    if (all || p->pending.size() - k > 256) { if (hipEventSynchronize(t.e1) != hipSuccess) break; }
+    else if (hipEventQuery(t.e1) != hipSuccess) break;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) { p->duration[t.which] += 1e-3 * ms; p->number[t.which] += t.count; }
+    p->spare.push_back(t);
+  }
+  (void)hipGetLastError();      // (hipErrorNotReady from the query is not an error of the caller)
+  p->pending.erase(p->pending.begin(), p->pending.begin() + k);
+}
+static void prof_free(Profiler* p) {
+  (void)hipDeviceSynchronize();
+  for (auto* v : {&p->pending, &p->spare}) for (TimerPair& t : *v) { (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); }
+  delete p;
+}
+static bool prof_begin(dmc_batch* b, hipStream_t stream, TimerPair* t) {
+  Profiler* p = b->prof;
+  if (!p || !p->on) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
+  prof_drain(p, false);
+  if (!p->spare.empty()) { *t = p->spare.back(); p->spare.pop_back(); }
+  else if (hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess) return false;
+  return hipEventRecord(t->e0, stream) == hipSuccess;
+}
+static void prof_end(dmc_batch* b, hipStream_t stream, TimerPair t, int which, int count) {
+  t.which = which; t.count = count;
+  if (hipEventRecord(t.e1, stream) == hipSuccess) b->prof->pending.push_back(t); else b->prof->spare.push_back(t);
+}
+static void xfer_free(Xfer* x) {
+  (void)hipDeviceSynchronize();
+  for (int k = 0; k < Xfer::kSlots; k++) { if (x->h_in[k]) (void)hipHostFree(x->h_in[k]); if (x->d_in[k]) (void)hipFree(x->d_in[k]); if (x->ev_in[k]) (void)hipEventDestroy(x->ev_in[k]); }
+  if (x->h_out) (void)hipHostFree(x->h_out);
+  if (x->d_out) (void)hipFree(x->d_out);
+  if (x->ev_out) (void)hipEventDestroy(x->ev_out);
+  delete x;
 }
 
 static int choose_geometry(dmc_batch* b, int lanes_per_env) {
@@ -182,32 +274,40 @@ extern "C" int dmc_batch_create(const dmc_model* m, int batch_size, int device_i
   const int caps[3] = {nconmax, njmax, lanes_per_env};
   return dmc_batch_create_caps(m, batch_size, device_id, precision, caps, 3, out);
 }
-extern "C" int dmc_batch_create_caps(const dmc_model* m, int batch_size, int device_id, int precision,
-                                     const int* caps, int ncaps, dmc_batch** out) {
-  if (ncaps < 0 || (ncaps > 0 && !caps)) return fail("null argument");
-  const int nconmax = ncaps > 0 ? caps[0] : 0, njmax = ncaps > 1 ? caps[1] : 0, lanes_per_env = ncaps > 2 ? caps[2] : 0;
-  const int njcon = ncaps > 3 ? caps[3] : 0;
-  int jlevel = ncaps > 4 ? caps[4] - 1 : -1;      // caps[4]: StepDims::jglobal + 1, 0 = automatic
-  if (!m || !out) return fail("null argument");
-  if (batch_size < 1) return fail("batch_size must be >= 1");
-  if (precision != 32 && precision != 64) return fail("precision must be 32 or 64");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: the batched step has no CPU fallback", -3);
-  if (device_id < 0 || device_id >= ndev) return fail("invalid device id");
-  HIP_TRY(hipSetDevice(device_id));
-  dmc_batch* b = new dmc_batch();
-  b->model = m; b->B = batch_size; b->device = device_id; b->precision = precision;
-  b->elem = precision == 64 ? sizeof(double) : sizeof(float);
-  b->outmask = OUT_ALL; b->ndebug = 0; b->d_debug = nullptr; b->d_debug_i = nullptr; b->d_mi = nullptr; b->d_mc = nullptr; b->d_mr = nullptr; b->d_stash_r = nullptr; b->d_stash_i = nullptr; b->d_epoch = nullptr; b->stash_on = 0; b->stash_auto = 0; b->d_eg_slot = nullptr; b->xfrc_on = 0; b->d_ns_A = nullptr; b->d_gscr = nullptr; b->d_work = nullptr; b->d_kstash = nullptr; b->d_kstash_i = nullptr; b->d_cost = nullptr; b->d_order = nullptr; b->lpt = 0; b->nitems = 0; b->d_prof = nullptr; b->d_layout = nullptr; b->d_trace = nullptr; b->trace_launch = 0; b->d_rj_i = nullptr; b->d_rj_r = nullptr;
+// the data fields of DMC_DATA_*_FIELDS, zeroed
+static int create_fields(dmc_batch* b) {
+  const StepDims& d = b->tb.L.d;
+  const int nq = d.nq, nv = d.nv, nu = d.nu, na = d.na, nbody = d.nbody, ngeom = d.ngeom, nsite = d.nsite,
+            nsensordata = d.nsensordata, nmocap = d.nmocap, nconmax = d.nconmax;
+  auto add = [&](FieldId id, const char* name, int rows, bool is_int, int flags) {
+    Field& f = b->fields[id];
+    f.name = name; f.rows = rows; f.is_int = is_int; f.flags = flags;
+    const size_t es = is_int ? sizeof(int) : ((flags & DMC_FIELD_F64) ? sizeof(double) : b->elem);
+    if (dev_alloc(b, &f.owned, (size_t)std::max(1, rows) * b->B * es, true, "field")) return -2;
+    f.dev = f.owned;
+    return 0;
+  };
+#define X(name, count, flags) if (add(F_##name, #name, count, false, flags)) return -2;
+  DMC_DATA_REAL_FIELDS(X)
+#undef X
+#define X(name, count, flags) if (add(F_##name, #name, count, true, flags)) return -2;
+  DMC_DATA_INT_FIELDS(X)
+#undef X
+  return 0;
+}
+// (what dmc_batch_create_caps does to the new batch: any failure returns, and the caller destroys the batch)
+static int batch_init(dmc_batch* b, int nconmax, int njmax, int lanes_per_env, int njcon, int jlevel) {
+  const dmc_model* m = b->model;
+  const int batch_size = b->B;
   std::string err;
-  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || ncu < 1) ncu = 256; b->ncu = ncu; }
+  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || ncu < 1) ncu = 256; b->ncu = ncu; }
   // The contact rows and the kept factor of M leave LDS for the per-env global scratch on the 17 .. 32-dof models so that
   // more environments are resident per CU (level 1: config 3 +24 %).  A batch of at most one environment per CU has
   // nothing to gain from residency and pays a global round trip wherever a row is read: it keeps them in LDS
   // (soccer 2v2, B = 256: +3 %; at B = 4096 the same choice costs 8 %).  DMC_JLEVEL=<n>: tuning override.
   if (jlevel < 0 && getenv("DMC_JLEVEL")) jlevel = atoi(getenv("DMC_JLEVEL"));
   const bool small_auto = jlevel < 0 && batch_size <= b->ncu && DMC_JGLOBAL_LEVEL(m->hm.nv) == 1;
-  if (!step_tables_build(&b->tb, m->hm, nconmax, njmax, &err, njcon, small_auto ? 0 : jlevel)) { delete b; return fail(err); }
+  if (!step_tables_build(&b->tb, m->hm, nconmax, njmax, &err, njcon, small_auto ? 0 : jlevel)) return fail(err);
   if (small_auto) {
     // ... unless only the default layout has a baked model-specialised kernel (the generic one is 2 - 3 x slower: that
     // would be a bad trade for a global round trip per row)
@@ -221,40 +321,29 @@ extern "C" int dmc_batch_create_caps(const dmc_model* m, int batch_size, int dev
         b->tb = def;
         const bool def_fits = choose_geometry(b, lanes_per_env) == 0;
         if (fits && (!def_fits || b->geom.static_id < 0)) { b->tb = keep; b->geom = kg; }
-      } else if (!fits) { delete b; return fail(err); }
+      } else if (!fits) return fail(err);
     }
   }
-  if (choose_geometry(b, lanes_per_env)) { delete b; return -1; }
+  if (choose_geometry(b, lanes_per_env)) return -1;
   const StepLayout& L = b->tb.L;
   const StepDims& d = L.d;
-  hipError_t e = hipMalloc(&b->d_mi, (size_t)L.n_mi * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&b->d_mc, b->tb.mc.size() * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&b->d_mr, (size_t)L.n_mr * b->elem);
-  if (e == hipSuccess) e = hipMalloc((void**)&b->d_layout, sizeof(StepLayout));
-  if (e == hipSuccess) e = hipMemcpy(b->d_layout, &L, sizeof(StepLayout), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { delete b; return fail(std::string("hipMalloc: ") + hipGetErrorString(e), -2); }
-  if (upload_tables(b)) { delete b; return -2; }
+  if (dev_alloc(b, &b->d_mi, (size_t)L.n_mi * sizeof(int), false, "") || dev_alloc(b, &b->d_mc, b->tb.mc.size() * sizeof(int), false, "") ||
+      dev_alloc(b, &b->d_mr, (size_t)L.n_mr * b->elem, false, "") || dev_alloc(b, &b->d_layout, sizeof(StepLayout), false, "", &L)) return -2;
+  if (upload_tables(b)) return -2;
   b->tb.opts.g_mr = b->d_mr;
   if (d.nslip) {
-    e = hipMalloc(&b->d_ns_A, (size_t)b->B * d.nslip * d.nslip * b->elem);
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc noslip matrix: ") + hipGetErrorString(e), -2); }
+    if (dev_alloc(b, &b->d_ns_A, (size_t)b->B * d.nslip * d.nslip * b->elem, false, "noslip matrix")) return -2;
     b->tb.opts.ns_A = b->d_ns_A;
   }
-  { const int one = 1;
-    e = hipMalloc((void**)&b->d_epoch, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(b->d_epoch, &one, sizeof(int), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc stash epoch: ") + hipGetErrorString(e), -2); } }
+  const int one = 1;
+  if (dev_alloc(b, &b->d_epoch, sizeof(int), false, "stash epoch", &one)) return -2;
   // work[1]: finished waves; work[32 (1 + x)]: head of XCD x's queue (a 128-byte line each)
-  e = hipMalloc((void**)&b->d_work, 32 * 9 * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(b->d_work, 0, 32 * 9 * sizeof(int));
-  if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc work queue: ") + hipGetErrorString(e), -2); }
+  if (dev_alloc(b, &b->d_work, 32 * 9 * sizeof(int), true, "work queue")) return -2;
   // (a mocap pose is an input of mj_kinematics that the stash's (qpos, qvel) comparison does not see: no stash for those models)
   if (!getenv("DMC_NO_KSTASH") && !d.nmocap) {
     const size_t nk = (size_t)d.nq + d.nv + (L.s_qM - L.s_xpos);
-    e = hipMalloc(&b->d_kstash, (size_t)b->B * nk * b->elem);
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_kstash_i, (size_t)b->B * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(b->d_kstash_i, 0, (size_t)b->B * sizeof(int));      // epoch 0: never valid
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc kinematic stash: ") + hipGetErrorString(e), -2); }
+    if (dev_alloc(b, &b->d_kstash, (size_t)b->B * nk * b->elem, false, "kinematic stash") ||
+        dev_alloc(b, &b->d_kstash_i, (size_t)b->B * sizeof(int), true, "kinematic stash")) return -2;      // epoch 0: never valid
   }
   if (b->geom.queue) {
     // queued step launches of several physics steps hand an item out in pieces (StepIO::slices; DMC_SLICES=<n>: at most n
@@ -270,110 +359,65 @@ extern "C" int dmc_batch_create_caps(const dmc_model* m, int batch_size, int dev
     b->max_slices = getenv("DMC_SLICES") ? atoi(getenv("DMC_SLICES")) : (one_l2_per_queue ? 8 : 1);
     auto hw = [&](int n) { return b->precision == 64 ? n : (n + 1) / 2; };
     b->hand_n = hw(d.nq) + 2 * hw(d.nv) + hw(d.na) + 1;
-    e = hipMalloc((void**)&b->d_prog, (size_t)nit * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(b->d_prog, 0, (size_t)nit * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_hand, (size_t)b->B * b->hand_n * sizeof(unsigned long long));
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc piece counters: ") + hipGetErrorString(e), -2); }
+    if (dev_alloc(b, &b->d_prog, (size_t)nit * sizeof(int), true, "piece counters") ||
+        dev_alloc(b, &b->d_hand, (size_t)b->B * b->hand_n * sizeof(unsigned long long), false, "piece counters")) return -2;
   }
   if (b->geom.queue && !getenv("DMC_NO_LPT")) {
     b->nitems = (b->B * b->geom.lpe + 63) / 64;
-    e = hipMalloc((void**)&b->d_cost, (size_t)b->nitems * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(b->d_cost, 0, (size_t)b->nitems * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&b->d_order, (size_t)b->nitems * sizeof(int));
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc schedule: ") + hipGetErrorString(e), -2); }
+    if (dev_alloc(b, &b->d_cost, (size_t)b->nitems * sizeof(int), true, "schedule") ||
+        dev_alloc(b, &b->d_order, (size_t)b->nitems * sizeof(int), false, "schedule")) return -2;
     b->lpt = 1;
   }
   if (L.n_gs) {
-    const size_t bytes = (size_t)b->B * L.n_gs * b->elem;
-    e = hipMalloc(&b->d_gscr, bytes);
-    if (e == hipSuccess) e = hipMemset(b->d_gscr, 0, bytes);
-    if (e != hipSuccess) { dmc_batch_destroy(b); return fail(std::string("hipMalloc global scratch: ") + hipGetErrorString(e), -2); }
+    if (dev_alloc(b, &b->d_gscr, (size_t)b->B * L.n_gs * b->elem, true, "global scratch")) return -2;
     b->tb.opts.gscr = b->d_gscr;
   }
-  struct Spec { const char* name; int rows; bool is_int; };
-  const int nb = d.nbody;
-  const Spec specs[] = {
-      {"qpos", d.nq, false}, {"qvel", d.nv, false}, {"ctrl", d.nu, false}, {"qacc_warmstart", d.nv, false},
-      {"qfrc_applied", d.nv, false}, {"xfrc_applied", 6*nb, false}, {"time", 1, false}, {"act", d.na, false},
-      {"mocap_pos", 3*d.nmocap, false}, {"mocap_quat", 4*d.nmocap, false},
-      {"sensordata", d.nsensordata, false}, {"xpos", 3*nb, false}, {"xquat", 4*nb, false}, {"xmat", 9*nb, false},
-      {"xipos", 3*nb, false}, {"geom_xpos", 3*d.ngeom, false}, {"geom_xmat", 9*d.ngeom, false},
-      {"site_xpos", 3*d.nsite, false}, {"site_xmat", 9*d.nsite, false}, {"subtree_com", 3*nb, false},
-      {"qacc", d.nv, false}, {"actuator_force", d.nu, false}, {"qfrc_actuator", d.nv, false},
-      {"qfrc_bias", d.nv, false}, {"qfrc_constraint", d.nv, false},
-      {"contact_dist", d.nconmax, false}, {"contact_pos", 3*d.nconmax, false}, {"contact_frame", 9*d.nconmax, false},
-      {"contact_force", 6*d.nconmax, false}, {"cvel", 6*nb, false},
-      {"ncon", 1, true}, {"nefc", 1, true}, {"solver_iter", 1, true}, {"warning", DMC_NWARNING, true},
-      {"contact_geom1", d.nconmax, true}, {"contact_geom2", d.nconmax, true}, {"env_mode", 1, true}};
-  for (const Spec& s : specs) {
-    Field f; f.name = s.name; f.rows = s.rows; f.is_int = s.is_int; f.is_f64 = !strcmp(s.name, "time"); f.dev = nullptr; f.owned = nullptr;
-    const size_t bytes = (size_t)std::max(1, s.rows) * b->B * (s.is_int ? sizeof(int) : (f.is_f64 ? sizeof(double) : b->elem));
-    e = hipMalloc(&f.owned, bytes);
-    if (e == hipSuccess) e = hipMemset(f.owned, 0, bytes);
-    if (e != hipSuccess) { *out = nullptr; dmc_batch_destroy(b); return fail(std::string("hipMalloc field: ") + hipGetErrorString(e), -2); }
-    f.dev = f.owned;
-    b->index[f.name] = (int)b->fields.size();
-    b->fields.push_back(f);
-  }
-  *out = b;
+  if (create_fields(b)) return -2;
   // The stash of the position / velocity stage between legacy steps is opt-in (option "stash", or DMC_STASH=1):
   // measured on MI355X (cheetah, B = 4096) the 2 x 7.3 KB per env of stash traffic cost more than the partial
   // trailing pass it replaces (0.139 vs 0.134 ms per launch).
-  if (getenv("DMC_STASH") && atoi(getenv("DMC_STASH"))) { if (dmc_batch_set_opt_int(b, "stash", 1)) { dmc_batch_destroy(b); *out = nullptr; return -2; } }
+  if (getenv("DMC_STASH") && atoi(getenv("DMC_STASH")) && dmc_batch_set_opt_int(b, "stash", 1)) return -2;
   return dmc_batch_reset(b, nullptr, -1);
 }
+extern "C" int dmc_batch_create_caps(const dmc_model* m, int batch_size, int device_id, int precision,
+                                     const int* caps, int ncaps, dmc_batch** out) {
+  if (ncaps < 0 || (ncaps > 0 && !caps)) return fail("null argument");
+  const int nconmax = ncaps > 0 ? caps[0] : 0, njmax = ncaps > 1 ? caps[1] : 0, lanes_per_env = ncaps > 2 ? caps[2] : 0;
+  const int njcon = ncaps > 3 ? caps[3] : 0;
+  const int jlevel = ncaps > 4 ? caps[4] - 1 : -1;      // caps[4]: StepDims::jglobal + 1, 0 = automatic
+  if (!m || !out) return fail("null argument");
+  *out = nullptr;
+  if (batch_size < 1) return fail("batch_size must be >= 1");
+  if (precision != 32 && precision != 64) return fail("precision must be 32 or 64");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: the batched step has no CPU fallback", -3);
+  if (device_id < 0 || device_id >= ndev) return fail("invalid device id");
+  HIP_TRY(hipSetDevice(device_id));
+  dmc_batch* b = new dmc_batch();
+  b->model = m; b->B = batch_size; b->device = device_id; b->precision = precision;
+  b->elem = precision == 64 ? sizeof(double) : sizeof(float);
+  const int rc = batch_init(b, nconmax, njmax, lanes_per_env, njcon, jlevel);
+  if (rc) { dmc_batch_destroy(b); return rc; }      // (g_err is the failure's: destroying sets none)
+  *out = b;
+  return 0;
+}
 
-static void prof_free(struct Profiler* p);
-static void xfer_free(struct Xfer* x);
 extern "C" void dmc_batch_destroy(dmc_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  if (b->prof) { prof_free(b->prof); b->prof = nullptr; }
-  if (b->xfer) { xfer_free(b->xfer); b->xfer = nullptr; }
-  for (Field& f : b->fields) if (f.owned) (void)hipFree(f.owned);
-  if (b->d_mi) (void)hipFree(b->d_mi);
-  if (b->d_mc) (void)hipFree(b->d_mc);
-  if (b->d_mr) (void)hipFree(b->d_mr);
-  if (b->d_layout) (void)hipFree(b->d_layout);
-  if (b->d_debug) (void)hipFree(b->d_debug);
-  if (b->d_debug_i) (void)hipFree(b->d_debug_i);
-  if (b->d_prof) (void)hipFree(b->d_prof);
-  if (b->d_stash_r) (void)hipFree(b->d_stash_r);
-  if (b->d_stash_i) (void)hipFree(b->d_stash_i);
-  if (b->d_epoch) (void)hipFree(b->d_epoch);
-  if (b->d_eg_slot) (void)hipFree(b->d_eg_slot);
-  if (b->d_ns_A) (void)hipFree(b->d_ns_A);
-  if (b->d_gscr) (void)hipFree(b->d_gscr);
-  if (b->d_work) (void)hipFree(b->d_work);
-  if (b->d_kstash) (void)hipFree(b->d_kstash);
-  if (b->d_kstash_i) (void)hipFree(b->d_kstash_i);
-  if (b->d_cost) (void)hipFree(b->d_cost);
-  if (b->d_order) (void)hipFree(b->d_order);
-  if (b->d_prog) (void)hipFree(b->d_prog);
-  if (b->d_hand) (void)hipFree(b->d_hand);
-  if (b->d_task_args) (void)hipFree(b->d_task_args);
-  if (b->d_trace) (void)hipFree(b->d_trace);
-  if (b->d_rj_i) (void)hipFree(b->d_rj_i);
-  if (b->d_rj_r) (void)hipFree(b->d_rj_r);
+  if (b->prof) prof_free(b->prof);
+  if (b->xfer) xfer_free(b->xfer);
+  for (void* p : b->dev_bufs) (void)hipFree(p);
   delete b;
 }
 
 template <typename T>
 static void fill_io(dmc_batch* b, StepIO<T>* io) {
-  auto P = [&](const char* n) { return find_field(b, n)->dev; };
   io->B = b->B;
-  io->qpos = (T*)P("qpos"); io->qvel = (T*)P("qvel"); io->ctrl = (T*)P("ctrl");
-  io->qacc_warmstart = (T*)P("qacc_warmstart"); io->qfrc_applied = (T*)P("qfrc_applied"); io->time = (double*)P("time"); io->act = (T*)P("act"); io->prof = b->d_prof;
-  io->sensordata = (T*)P("sensordata"); io->xpos = (T*)P("xpos"); io->xquat = (T*)P("xquat"); io->xmat = (T*)P("xmat");
-  io->xipos = (T*)P("xipos"); io->geom_xpos = (T*)P("geom_xpos"); io->geom_xmat = (T*)P("geom_xmat");
-  io->site_xpos = (T*)P("site_xpos"); io->site_xmat = (T*)P("site_xmat"); io->subtree_com = (T*)P("subtree_com");
-  io->qacc = (T*)P("qacc"); io->actuator_force = (T*)P("actuator_force"); io->qfrc_actuator = (T*)P("qfrc_actuator");
-  io->qfrc_bias = (T*)P("qfrc_bias"); io->qfrc_constraint = (T*)P("qfrc_constraint");
-  io->contact_dist = (T*)P("contact_dist"); io->contact_pos = (T*)P("contact_pos"); io->contact_frame = (T*)P("contact_frame");
-  io->contact_force = (T*)P("contact_force"); io->cvel = (T*)P("cvel");
-  io->ncon = (int*)P("ncon"); io->nefc = (int*)P("nefc"); io->solver_iter = (int*)P("solver_iter");
-  io->warning = (int*)P("warning"); io->contact_geom1 = (int*)P("contact_geom1"); io->contact_geom2 = (int*)P("contact_geom2");
-  io->env_mode = (const int*)P("env_mode");
+#define X(name, count, flags) if constexpr (!((flags) & DMC_FIELD_OPTS)) io->name = (decltype(io->name))b->fields[F_##name].dev;
+  DMC_DATA_REAL_FIELDS(X) DMC_DATA_INT_FIELDS(X)
+#undef X
+  io->prof = b->d_prof;
   io->work = b->geom.queue ? b->d_work : nullptr;
   io->cost = b->lpt ? b->d_cost : nullptr; io->order = b->lpt ? b->d_order : nullptr;
   io->prog = nullptr; io->slices = 0; io->hand = b->d_hand; io->hand_n = b->hand_n;      // (slices: launch_untimed, step launches of a queued batch only)
@@ -410,109 +454,59 @@ __global__ void __launch_bounds__(1024) order_kernel(const int* __restrict__ cos
 }
 
 struct SeqArgs { const void* ctrl; void* qpos; void* qvel; void* sensor; int nsub; };
-// ---- profiling contract (mujoco/engine.py:135-137 enable_profiling -> wrapper.enable_timer; mjData.timer[]) ------
-// MuJoCo brackets mj_step / mj_forward with the mjcb_time callback and accumulates duration and call count per timer.
-// Here a launch IS the step: with profiling enabled every launch is bracketed by two hipEvents on its stream; the pairs
-// are resolved lazily (completed ones whenever a new launch is issued, all of them when the timer is read), so an
-// asynchronous caller is not serialised.  Launches recorded into a HIP graph are not timed (events cannot be queried
-// across replays).
-struct TimerPair { hipEvent_t e0, e1; int which, count; };
-struct Profiler {
-  bool on = false;
-  double duration[2] = {0, 0};      // seconds: [mjTIMER_STEP, mjTIMER_FORWARD]
-  long long number[2] = {0, 0};
-  std::vector<TimerPair> pending, spare;
-};
-static void prof_drain(Profiler* p, bool all) {
-  size_t k = 0;
-  for (; k < p->pending.size(); k++) {
-    TimerPair& t = p->pending[k];
-    if (all || p->pending.size() - k > 256) { if (hipEventSynchronize(t.e1) != hipSuccess) break; }
-    else if (hipEventQuery(t.e1) != hipSuccess) break;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) { p->duration[t.which] += 1e-3 * ms; p->number[t.which] += t.count; }
-    p->spare.push_back(t);
-  }
-  (void)hipGetLastError();      // (hipErrorNotReady from the query is not an error of the caller)
-  p->pending.erase(p->pending.begin(), p->pending.begin() + k);
-}
-static void prof_free(Profiler* p) {
-  (void)hipDeviceSynchronize();
-  for (auto* v : {&p->pending, &p->spare}) for (TimerPair& t : *v) { (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); }
-  delete p;
-}
-static bool prof_begin(dmc_batch* b, hipStream_t stream, TimerPair* t) {
-  Profiler* p = b->prof;
-  if (!p || !p->on) return false;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
-  prof_drain(p, false);
-  if (!p->spare.empty()) { *t = p->spare.back(); p->spare.pop_back(); }
-  else if (hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess) return false;
-  return hipEventRecord(t->e0, stream) == hipSuccess;
-}
-static void prof_end(dmc_batch* b, hipStream_t stream, TimerPair t, int which, int count) {
-  t.which = which; t.count = count;
-  if (hipEventRecord(t.e1, stream) == hipSuccess) b->prof->pending.push_back(t); else b->prof->spare.push_back(t);
-}
-static int launch_untimed(dmc_batch* b, int nstep, int legacy, int mode, void* stream, const SeqArgs* sq);
-static int launch(dmc_batch* b, int nstep, int legacy, int mode, void* stream, const SeqArgs* sq = nullptr) {
-  HIP_TRY(hipSetDevice(b->device));
-  TimerPair t;
-  const bool timed = prof_begin(b, (hipStream_t)stream, &t);
-  const int rc = launch_untimed(b, nstep, legacy, mode, stream, sq);
-  // mjTIMER_STEP counts mj_step calls: a launch of mode 0 / 3 runs nstep (x n_sub_steps) of them; mj_step1 / mj_step2
-  // launches count as one step per pair (on the mj_step2 half); mj_forward launches go to mjTIMER_FORWARD
-  if (timed) prof_end(b, (hipStream_t)stream, t, (mode == 1 || mode == 2) ? 1 : 0,
-                      mode == 0 ? nstep : mode == 3 ? nstep * (sq ? sq->nsub : 1) : mode == 5 ? 1 : mode == 4 ? 0 : 1);
-  return rc;
-}
-static int launch_untimed(dmc_batch* b, int nstep, int legacy, int mode, void* stream, const SeqArgs* sq) {
-  HIP_TRY(hipSetDevice(b->device));
-  b->launched_mask = b->outmask;      // what the derived arrays in HBM hold from now on (dmc_camera_render checks it)
-  if (b->tb.opts.eg_n) b->tb.opts.eg_data = find_field(b, "env_geom")->dev;      // follows dmc_batch_bind
-  b->tb.opts.xfrc = b->xfrc_on ? find_field(b, "xfrc_applied")->dev : nullptr; b->tb.opts.xfrc_B = b->B;
-  if (b->tb.L.d.nmocap) { b->tb.opts.mocap_pos = find_field(b, "mocap_pos")->dev; b->tb.opts.mocap_quat = find_field(b, "mocap_quat")->dev; b->tb.opts.mocap_B = b->B; }      // follow dmc_batch_bind
-  hipError_t e;
+template <typename T>
+static int launch_t(dmc_batch* b, int nstep, int legacy, LaunchMode mode, void* stream, const SeqArgs* sq) {
+  StepOpts<double>& opts = b->tb.opts;
+  if (opts.eg_n) opts.eg_data = b->fields[F_env_geom].dev;      // follows dmc_batch_bind
+  opts.xfrc = b->xfrc_on ? b->fields[F_xfrc_applied].dev : nullptr; opts.xfrc_B = b->B;
+  if (b->tb.L.d.nmocap) { opts.mocap_pos = b->fields[F_mocap_pos].dev; opts.mocap_quat = b->fields[F_mocap_quat].dev; opts.mocap_B = b->B; }      // follow dmc_batch_bind
   const int nsub = sq ? sq->nsub : 1;
   // pieces of a queued Physics.step(nstep) launch (never with the full stash, whose trailing stage belongs to the last step)
   // (models of more than 16 dofs: the kernels of the small ones are built without the hand-off code, step_core.h kSlices)
-  const int slices = (b->geom.queue && b->d_prog && mode == 0 && !b->stash_on && b->tb.L.d.nv > 16) ? std::min(nstep, b->max_slices) : 1;
+  const int slices = (b->geom.queue && b->d_prog && mode == MODE_STEP && !b->stash_on && b->tb.L.d.nv > 16) ? std::min(nstep, b->max_slices) : 1;
   // a specialisation plugin takes the launch unless it was built lean and the launch needs an optional feature
   const bool need_feat = legacy == 2 || b->d_probe != nullptr || b->tb.opts.integrator == DMC_INT_IMPLICITFAST;
   const bool spec = b->spec_launch && (b->spec_features || !need_feat);
   // ... but a kernel with a task epilogue (suite/fused_env.py) is the only one that runs the task layer: the library's own
   // kernel would step the physics and leave observation, reward, flags and step counters as they were, without a word
-  if (b->task_on && mode == 0 && !spec)
+  if (b->task_on && mode == MODE_STEP && !spec)
     return fail("the task kernel was built without the optional launch features this launch needs (a substep probe, legacy_step 2 or the "
                 "implicitfast integrator): it cannot take the launch, and no other kernel runs the task layer");
   // longest-first hand-out pays for whole items only: with pieces a launch ends within one piece of the last claim whatever
   // the order (round 6, one box: config 3 +1.4 % without the 16 us ordering kernel in front of every launch, config 4 -0.2 %)
   if (b->lpt && slices <= 1) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)b->d_cost, b->d_order, b->nitems);
-  if (b->precision == 64) {
-    StepIO<double> io; fill_io(b, &io);
-    if (slices > 1) { io.prog = b->d_prog; io.slices = slices; io.cost = nullptr; io.order = nullptr; }
-    io.ctrl_seq = sq ? (const double*)sq->ctrl : nullptr; io.qpos_seq = sq ? (double*)sq->qpos : nullptr;
-    io.qvel_seq = sq ? (double*)sq->qvel : nullptr; io.sensor_seq = sq ? (double*)sq->sensor : nullptr;
-    if (spec) {
-      typedef int (*fn_t)(const LaunchGeom*, void*, const StepLayout*, const StepOpts<double>*, const int*, const double*, const int*, const StepIO<double>*, int, int, int, int, int);
-      e = (hipError_t)((fn_t)b->spec_launch)(&b->geom, stream, b->d_layout, &b->tb.opts, b->d_mi, (const double*)b->d_mr, b->d_mc, &io, nstep, legacy, mode, b->outmask, nsub);
-    } else
-    e = launch_step_f64(b->geom, (hipStream_t)stream, b->d_layout, b->tb.opts, b->d_mi, (const double*)b->d_mr, b->d_mc, io, nstep, legacy, mode, b->outmask, nsub);
-  } else {
-    StepIO<float> io; fill_io(b, &io);
-    if (slices > 1) { io.prog = b->d_prog; io.slices = slices; io.cost = nullptr; io.order = nullptr; }
-    io.ctrl_seq = sq ? (const float*)sq->ctrl : nullptr; io.qpos_seq = sq ? (float*)sq->qpos : nullptr;
-    io.qvel_seq = sq ? (float*)sq->qvel : nullptr; io.sensor_seq = sq ? (float*)sq->sensor : nullptr;
-    if (spec) {
-      typedef int (*fn_t)(const LaunchGeom*, void*, const StepLayout*, const StepOpts<float>*, const int*, const float*, const int*, const StepIO<float>*, int, int, int, int, int);
-      const StepOpts<float> of = step_opts_cast<float>(b->tb.opts);
-      e = (hipError_t)((fn_t)b->spec_launch)(&b->geom, stream, b->d_layout, &of, b->d_mi, (const float*)b->d_mr, b->d_mc, &io, nstep, legacy, mode, b->outmask, nsub);
-    } else
-    e = launch_step_f32(b->geom, (hipStream_t)stream, b->d_layout, step_opts_cast<float>(b->tb.opts), b->d_mi, (const float*)b->d_mr, b->d_mc, io, nstep, legacy, mode, b->outmask, nsub);
-  }
+  StepIO<T> io; fill_io(b, &io);
+  if (slices > 1) { io.prog = b->d_prog; io.slices = slices; io.cost = nullptr; io.order = nullptr; }
+  io.ctrl_seq = sq ? (const T*)sq->ctrl : nullptr; io.qpos_seq = sq ? (T*)sq->qpos : nullptr;
+  io.qvel_seq = sq ? (T*)sq->qvel : nullptr; io.sensor_seq = sq ? (T*)sq->sensor : nullptr;
+  constexpr bool f64 = sizeof(T) == sizeof(double);
+  StepOpts<T> cast; const StepOpts<T>* o;      // (fp64: the batch's own options, as they are)
+  if constexpr (f64) o = &opts; else { cast = step_opts_cast<T>(opts); o = &cast; }
+  hipError_t e;
+  if (spec) {
+    typedef int (*fn_t)(const LaunchGeom*, void*, const StepLayout*, const StepOpts<T>*, const int*, const T*, const int*, const StepIO<T>*, int, int, int, int, int);
+    e = (hipError_t)((fn_t)b->spec_launch)(&b->geom, stream, b->d_layout, o, b->d_mi, (const T*)b->d_mr, b->d_mc, &io, nstep, legacy, mode, b->outmask, nsub);
+  } else if constexpr (f64) e = launch_step_f64(b->geom, (hipStream_t)stream, b->d_layout, *o, b->d_mi, (const T*)b->d_mr, b->d_mc, io, nstep, legacy, mode, b->outmask, nsub);
+  else e = launch_step_f32(b->geom, (hipStream_t)stream, b->d_layout, *o, b->d_mi, (const T*)b->d_mr, b->d_mc, io, nstep, legacy, mode, b->outmask, nsub);
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e), -2);
   return 0;
+}
+static int launch_untimed(dmc_batch* b, int nstep, int legacy, LaunchMode mode, void* stream, const SeqArgs* sq) {
+  HIP_TRY(hipSetDevice(b->device));
+  b->launched_mask = b->outmask;      // what the derived arrays in HBM hold from now on (dmc_camera_render checks it)
+  return b->precision == 64 ? launch_t<double>(b, nstep, legacy, mode, stream, sq) : launch_t<float>(b, nstep, legacy, mode, stream, sq);
+}
+static int launch(dmc_batch* b, int nstep, int legacy, LaunchMode mode, void* stream, const SeqArgs* sq = nullptr) {
+  HIP_TRY(hipSetDevice(b->device));
+  TimerPair t;
+  const bool timed = prof_begin(b, (hipStream_t)stream, &t);
+  const int rc = launch_untimed(b, nstep, legacy, mode, stream, sq);
+  // mjTIMER_STEP counts mj_step calls: a step / rollout launch runs nstep (x n_sub_steps) of them; mj_step1 / mj_step2
+  // launches count as one step per pair (on the mj_step2 half); mj_forward launches go to mjTIMER_FORWARD
+  const bool fwd = mode == MODE_FORWARD || mode == MODE_FORWARD_NOACT;
+  if (timed) prof_end(b, (hipStream_t)stream, t, fwd ? 1 : 0,
+                      mode == MODE_STEP ? nstep : mode == MODE_ROLLOUT ? nstep * (sq ? sq->nsub : 1) : mode == MODE_STEP1 ? 0 : 1);
+  return rc;
 }
 
 extern "C" int dmc_batch_attach_specialised(dmc_batch* b, const char* so_path) {
@@ -548,7 +542,7 @@ extern "C" int dmc_batch_set_task_args(dmc_batch* b, const void* args, int nbyte
   if (!b->spec_task_bytes) return fail("the batch's kernel carries no task epilogue (attach a plugin built with a task header)");
   if (nbytes != b->spec_task_bytes) return fail("task argument block: size differs from the one the kernel was generated with");
   HIP_TRY(hipSetDevice(b->device));
-  if (!b->d_task_args) HIP_TRY(hipMalloc(&b->d_task_args, (size_t)nbytes));
+  if (!b->d_task_args && dev_alloc(b, &b->d_task_args, (size_t)nbytes, false, "task arguments")) return -2;
   HIP_TRY(hipMemcpy(b->d_task_args, args, (size_t)nbytes, hipMemcpyHostToDevice));
   return 0;
 }
@@ -563,7 +557,7 @@ extern "C" int dmc_batch_step(dmc_batch* b, int nstep, int legacy_step, void* hi
   if (!b) return fail("null batch");
   if (nstep < 1) return fail("nstep must be >= 1");
   if (legacy_step == 2 && b->tb.opts.integrator == DMC_INT_RK4) return fail("legacy_step 2 (step + mj_forward) is not implemented for RK4 models");
-  return launch(b, nstep, legacy_step == 2 ? 2 : (legacy_step ? 1 : 0), 0, hip_stream);
+  return launch(b, nstep, legacy_step == 2 ? 2 : (legacy_step ? 1 : 0), MODE_STEP, hip_stream);
 }
 extern "C" int dmc_batch_set_step_probe(dmc_batch* b, int geom_id, void* out_dev, int capacity) {
   if (!b) return fail("null batch");
@@ -571,22 +565,6 @@ extern "C" int dmc_batch_set_step_probe(dmc_batch* b, int geom_id, void* out_dev
   if (geom_id < 0 || geom_id >= b->tb.L.d.ngeom) return fail("geom id out of range");
   b->d_probe = out_dev; b->probe_geom = geom_id; b->probe_cap = capacity;
   return 0;
-}
-struct Field;
-static int set_real(dmc_batch* b, Field* f, const double* src);
-// ---- per-environment model deltas: world-fixed geoms with per-env pose / size ---------------------------------
-// The reference randomises scenery per episode by editing the MJCF and recompiling (soccer RandomizedPitch,
-// locomotion/soccer/pitch.py:612-690 through composer's initialize_episode_mjcf); a batch shares one compiled model,
-// so the geoms that differ between environments get their pose and size from a per-env array instead of the tables.
-static double geom_rbound_of(int type, const double* size) {
-  switch (type) {
-    case DMC_GEOM_SPHERE: return size[0];
-    case DMC_GEOM_CAPSULE: return size[0] + size[1];
-    case DMC_GEOM_CYLINDER: return sqrt(size[0]*size[0] + size[1]*size[1]);
-    case DMC_GEOM_ELLIPSOID: return std::max(size[0], std::max(size[1], size[2]));
-    case DMC_GEOM_BOX: return sqrt(size[0]*size[0] + size[1]*size[1] + size[2]*size[2]);
-    default: return 0;
-  }
 }
 // The stash epoch (StepIO::epoch) is a device int: every edit that can change what the stashed stages depend on bumps
 // it with a one-thread kernel.  Host-synchronous entry points bump on the null stream and wait; dmc_batch_invalidate_async
@@ -597,69 +575,6 @@ static int bump_epoch(dmc_batch* b, hipStream_t stream, bool wait) {
   hipLaunchKernelGGL(epoch_bump_kernel, dim3(1), dim3(1), 0, stream, b->d_epoch);
   HIP_TRY(hipGetLastError());
   if (wait) HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
-}
-extern "C" int dmc_batch_set_env_geoms(dmc_batch* b, int n, const int* geom_ids) {
-  if (!b || n < 1 || !geom_ids) return fail("null argument");
-  if (find_field(b, "env_geom")) return fail("per-environment geoms were already declared for this batch");
-  const HostModel& m = b->model->hm;
-  std::vector<int> slot(m.ngeom, -1);
-  for (int k = 0; k < n; k++) {
-    const int g = geom_ids[k];
-    if (g < 0 || g >= m.ngeom) return fail("geom id out of range");
-    // world-fixed: on the worldbody, or on a jointless child of it whose frame is the world frame (PyMJCF attaches a
-    // static entity -- a goal -- as such a body; the per-environment row holds the geom's WORLD pose either way)
-    const int gb = m.geom_bodyid[g];
-    bool fixed = gb == 0;
-    if (!fixed && m.body_weldid[gb] == 0 && m.body_parentid[gb] == 0) {
-      const double* bp = &m.body_pos[3*gb]; const double* bq = &m.body_quat[4*gb];
-      fixed = bp[0] == 0 && bp[1] == 0 && bp[2] == 0 && bq[0] == 1 && bq[1] == 0 && bq[2] == 0 && bq[3] == 0;
-    }
-    if (!fixed) return fail("only world-fixed geoms (on the worldbody or on a jointless body at the world frame) can differ between environments");
-    if (slot[g] >= 0) return fail("geom listed twice");
-    slot[g] = k;
-  }
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  Field f; f.name = "env_geom"; f.rows = 16*n; f.is_int = false; f.is_f64 = false; f.dev = nullptr; f.owned = nullptr;
-  HIP_TRY(hipMalloc(&f.owned, (size_t)f.rows * b->B * b->elem));
-  f.dev = f.owned;
-  b->index[f.name] = (int)b->fields.size();
-  b->fields.push_back(f);
-  HIP_TRY(hipMalloc((void**)&b->d_eg_slot, sizeof(int) * m.ngeom));
-  HIP_TRY(hipMemcpy(b->d_eg_slot, slot.data(), sizeof(int) * m.ngeom, hipMemcpyHostToDevice));
-  // initial values: the model's own
-  std::vector<double> host((size_t)b->B * f.rows);
-  for (int k = 0; k < n; k++) {
-    const int g = geom_ids[k];
-    const double* q = &m.geom_quat[4*g];
-    double mat[9];
-    { const double w = q[0], x = q[1], y = q[2], z = q[3];
-      mat[0] = w*w + x*x - y*y - z*z; mat[4] = w*w - x*x + y*y - z*z; mat[8] = w*w - x*x - y*y + z*z;
-      mat[1] = 2*(x*y - w*z); mat[2] = 2*(x*z + w*y); mat[3] = 2*(x*y + w*z); mat[5] = 2*(y*z - w*x); mat[6] = 2*(x*z - w*y); mat[7] = 2*(y*z + w*x); }
-    double row[16];
-    for (int j = 0; j < 3; j++) row[j] = m.geom_pos[3*g + j];
-    for (int j = 0; j < 9; j++) row[3 + j] = mat[j];
-    for (int j = 0; j < 3; j++) row[12 + j] = m.geom_size[3*g + j];
-    row[15] = m.geom_rbound[g];
-    for (int e = 0; e < b->B; e++) for (int j = 0; j < 16; j++) host[(size_t)e * f.rows + 16*k + j] = row[j];
-  }
-  b->tb.opts.eg_slot = b->d_eg_slot; b->tb.opts.eg_n = n; b->tb.opts.eg_B = b->B;
-  if (bump_epoch(b, 0, true)) return -2;
-  return set_real(b, find_field(b, "env_geom"), host.data());
-}
-// rows of one geom slot from (pos, quat, size): what a caller writes into "env_geom" (host helper, no device work)
-extern "C" int dmc_env_geom_pack(int geom_type, const double* pos, const double* quat, const double* size, double* out16) {
-  if (!pos || !quat || !size || !out16) return fail("null argument");
-  const double n = sqrt(quat[0]*quat[0] + quat[1]*quat[1] + quat[2]*quat[2] + quat[3]*quat[3]);
-  if (!(n > 0)) return fail("zero quaternion");
-  const double w = quat[0]/n, x = quat[1]/n, y = quat[2]/n, z = quat[3]/n;
-  for (int j = 0; j < 3; j++) out16[j] = pos[j];
-  double* mat = out16 + 3;
-  mat[0] = w*w + x*x - y*y - z*z; mat[4] = w*w - x*x + y*y - z*z; mat[8] = w*w - x*x - y*y + z*z;
-  mat[1] = 2*(x*y - w*z); mat[2] = 2*(x*z + w*y); mat[3] = 2*(x*y + w*z); mat[5] = 2*(y*z - w*x); mat[6] = 2*(x*z - w*y); mat[7] = 2*(y*z + w*x);
-  for (int j = 0; j < 3; j++) out16[12 + j] = size[j];
-  out16[15] = geom_rbound_of(geom_type, size);
   return 0;
 }
 
@@ -674,27 +589,27 @@ static int ensure_stash(dmc_batch* b) {
 extern "C" int dmc_batch_step1(dmc_batch* b, void* hip_stream) {
   if (!b) return fail("null batch");
   if (ensure_stash(b)) return -2;
-  return launch(b, 1, 0, 4, hip_stream);
+  return launch(b, 1, 0, MODE_STEP1, hip_stream);
 }
 extern "C" int dmc_batch_step2(dmc_batch* b, void* hip_stream) {
   if (!b) return fail("null batch");
   if (b->tb.opts.integrator == DMC_INT_RK4) return fail("mj_step2 integrates with Euler only; RK4 models step through dmc_batch_step");
   if (ensure_stash(b)) return -2;
-  const int rc = launch(b, 1, 0, 5, hip_stream);
+  const int rc = launch(b, 1, 0, MODE_STEP2, hip_stream);
   // a stash this pair switched on is not left on for every later launch (2 x n_keep reals per env of traffic each)
   if (b->stash_auto) { b->stash_on = 0; b->stash_auto = 0; }
   return rc;
 }
 extern "C" int dmc_batch_forward(dmc_batch* b, int disable_actuation, void* hip_stream) {
   if (!b) return fail("null batch");
-  return launch(b, 0, 0, disable_actuation ? 2 : 1, hip_stream);
+  return launch(b, 0, 0, disable_actuation ? MODE_FORWARD_NOACT : MODE_FORWARD, hip_stream);
 }
 extern "C" int dmc_batch_rollout(dmc_batch* b, int nsteps, int n_sub_steps, const void* ctrl_seq, void* qpos_seq,
                                  void* qvel_seq, void* sensordata_seq, void* hip_stream) {
   if (!b) return fail("null batch");
   if (nsteps < 1 || n_sub_steps < 1) return fail("nsteps and n_sub_steps must be >= 1");
   SeqArgs sq = {ctrl_seq, qpos_seq, qvel_seq, sensordata_seq, n_sub_steps};
-  return launch(b, nsteps, 1, 3, hip_stream, &sq);
+  return launch(b, nsteps, 1, MODE_ROLLOUT, hip_stream, &sq);
 }
 // ---- observation gather table (composer/observation/updater.py:285-295, observable/mjcf.py:43) ---------------
 // An MJCFFeature observable is a named slice of an mjData field; a task's enabled observables resolve once into a
@@ -707,7 +622,7 @@ struct GatherPtrs { const void* p[16]; };
 struct dmc_gather {
   dmc_batch* batch;
   int nrows;
-  std::vector<std::string> field_names;   // distinct fields, slot order
+  std::vector<Field*> fields;   // distinct fields, slot order
   GatherRow* d_rows;
 };
 template <typename T>
@@ -748,11 +663,11 @@ extern "C" int dmc_gather_create(dmc_batch* b, int nrows, const char* const* fie
   for (int k = 0; k < nrows; k++) {
     Field* f = field_names[k] ? find_field(b, field_names[k]) : nullptr;
     if (!f) { delete g; return fail(std::string("unknown field: ") + (field_names[k] ? field_names[k] : "(null)")); }
-    if (f->is_int || f->is_f64) { delete g; return fail(std::string("field cannot be gathered (not in batch precision): ") + f->name); }
+    if (f->is_int || (f->flags & DMC_FIELD_F64)) { delete g; return fail(std::string("field cannot be gathered (not in batch precision): ") + f->name); }
     if (rows[k] < 0 || rows[k] >= f->rows) { delete g; return fail(std::string("row out of range for field ") + f->name); }
     int slot = -1;
-    for (size_t q = 0; q < g->field_names.size(); q++) if (g->field_names[q] == f->name) slot = (int)q;
-    if (slot < 0) { slot = (int)g->field_names.size(); g->field_names.push_back(f->name); }
+    for (size_t q = 0; q < g->fields.size(); q++) if (g->fields[q] == f) slot = (int)q;
+    if (slot < 0) { slot = (int)g->fields.size(); g->fields.push_back(f); }
     if (slot >= 16) { delete g; return fail("at most 16 distinct fields per gather table"); }
     const int op = ops ? ops[k] : GOP_NONE;
     if (op < GOP_NONE || op > GOP_ASINH) { delete g; return fail("unknown gather op"); }
@@ -775,7 +690,7 @@ extern "C" int dmc_gather_run(dmc_gather* g, void* out, void* hip_stream) {
   dmc_batch* b = g->batch;
   GatherPtrs ptrs;
   for (int q = 0; q < 16; q++) ptrs.p[q] = nullptr;
-  for (size_t q = 0; q < g->field_names.size(); q++) ptrs.p[q] = find_field(b, g->field_names[q].c_str())->dev;   // honours rebinding
+  for (size_t q = 0; q < g->fields.size(); q++) ptrs.p[q] = g->fields[q]->dev;   // honours rebinding
   HIP_TRY(hipSetDevice(b->device));
   // (row tiles across blockIdx.y while the batch alone does not fill the chip: at least ~2 workgroups per CU in flight)
   const int gx = (b->B + 63) / 64, ktiles = (g->nrows + 63) / 64;
@@ -795,64 +710,12 @@ extern "C" int dmc_batch_sync(dmc_batch* b) {
 }
 
 // ---- host <-> device field transfer (env-major host, SoA device) ------------------
-extern "C" int dmc_batch_set_async(dmc_batch* b, const char* name, const void* src, int host_bits, void* hip_stream);
-extern "C" int dmc_batch_get_async(dmc_batch* b, int n, const char* const* names, void* hip_stream);
-extern "C" int dmc_batch_get_wait(dmc_batch* b, int n, void* const* dsts, int host_bits);
-static bool get_in_flight(const dmc_batch* b);
-static int get_real(dmc_batch* b, Field* f, double* dst) {
-  const size_t n = (size_t)f->rows * b->B;
-  if (!n) return 0;
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (!get_in_flight(b)) {      // the pinned / device-transposed path, completed before returning
-    const char* nm = f->name.c_str();
-    if (dmc_batch_get_async(b, 1, &nm, nullptr)) return -2;
-    void* d = dst;
-    return dmc_batch_get_wait(b, 1, &d, 64);
-  }
-  if (b->precision == 64 || f->is_f64) {
-    std::vector<double> tmp(n);
-    HIP_TRY(hipMemcpy(tmp.data(), f->dev, n * sizeof(double), hipMemcpyDeviceToHost));
-    for (int k = 0; k < f->rows; k++) for (int e = 0; e < b->B; e++) dst[(size_t)e * f->rows + k] = tmp[(size_t)k * b->B + e];
-  } else {
-    std::vector<float> tmp(n);
-    HIP_TRY(hipMemcpy(tmp.data(), f->dev, n * sizeof(float), hipMemcpyDeviceToHost));
-    for (int k = 0; k < f->rows; k++) for (int e = 0; e < b->B; e++) dst[(size_t)e * f->rows + k] = tmp[(size_t)k * b->B + e];
-  }
-  return 0;
-}
-static int set_real(dmc_batch* b, Field* f, const double* src) {
-  const size_t n = (size_t)f->rows * b->B;
-  if (!n) return 0;
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  // (ctrl / qfrc_applied / xfrc_applied are inputs of the acceleration stage only; every other field bumps the stash epoch)
-  // the synchronous form of dmc_batch_set_async: pinned staging, device-side transposition, done before returning
-  if (dmc_batch_set_async(b, f->name.c_str(), src, 64, nullptr)) return -2;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return 0;
-}
 // ---- asynchronous host transfers -------------------------------------------------------------------------------
 // The host side of the boundary is env-major ((B, rows): what numpy callers hold), the device fields are SoA
 // ((rows, B)).  dmc_batch_set / dmc_batch_get transpose and convert element by element on one host thread around
 // synchronous pageable copies.  Here: the host only converts contiguously into PINNED staging (or not at all: fp32 on
 // the wire for fp32 batches), copies are hipMemcpyAsync on the caller's stream, the transposition is a device kernel
 // (LDS tile, coalesced on both sides), and a get of several fields is ONE device-to-host copy and one wait.
-struct Xfer {
-  static constexpr int kSlots = 4;
-  void* h_in[kSlots] = {}; void* d_in[kSlots] = {}; size_t cap_in[kSlots] = {}; hipEvent_t ev_in[kSlots] = {}; int next = 0;
-  void* h_out = nullptr; void* d_out = nullptr; size_t cap_out = 0; hipEvent_t ev_out = nullptr;
-  std::vector<std::pair<Field*, size_t>> pending;      // fields of the enqueued get and their offsets (elements) in the staging
-  bool out_in_flight = false;
-};
-static void xfer_free(Xfer* x) {
-  (void)hipDeviceSynchronize();
-  for (int k = 0; k < Xfer::kSlots; k++) { if (x->h_in[k]) (void)hipHostFree(x->h_in[k]); if (x->d_in[k]) (void)hipFree(x->d_in[k]); if (x->ev_in[k]) (void)hipEventDestroy(x->ev_in[k]); }
-  if (x->h_out) (void)hipHostFree(x->h_out);
-  if (x->d_out) (void)hipFree(x->d_out);
-  if (x->ev_out) (void)hipEventDestroy(x->ev_out);
-  delete x;
-}
 // out[c * ldo + r] = in[r * ldi + c] for r < nr, c < nc  (32 x 32 tiles through LDS).  `in` / `out` may be PINNED HOST
 // memory (device-mapped): the set kernel reads the caller's staged (B, rows) array over PCIe and the get kernel writes
 // the (B, rows) arrays straight into the host staging -- no separate hipMemcpyAsync on either side.
@@ -882,7 +745,7 @@ __global__ void __launch_bounds__(256) get_pack_kernel(GetTable t, int B) {
   else transpose_tile<float>((const float*)t.src[f], (float*)t.dst[f], t.rows[f], B, B, t.rows[f], blockIdx.x, blockIdx.y, (float (*)[33])tile64);
 }
 static bool get_in_flight(const dmc_batch* b) { return b->xfer && b->xfer->out_in_flight; }
-static size_t field_elem(const dmc_batch* b, const Field* f) { return f->is_int ? sizeof(int32_t) : (b->precision == 64 || f->is_f64) ? sizeof(double) : sizeof(float); }
+static size_t field_elem(const dmc_batch* b, const Field* f) { return f->is_int ? sizeof(int32_t) : (b->precision == 64 || (f->flags & DMC_FIELD_F64)) ? sizeof(double) : sizeof(float); }
 extern "C" int dmc_batch_set_async(dmc_batch* b, const char* name, const void* src, int host_bits, void* hip_stream) {
   if (!b || !name || !src) return fail("null argument");
   if (host_bits != 64 && host_bits != 32) return fail("host_bits must be 64 or 32");
@@ -913,8 +776,8 @@ extern "C" int dmc_batch_set_async(dmc_batch* b, const char* name, const void* s
   if (es == 8) launch_transpose<double>(hin, f->dev, b->B, f->rows, f->rows, b->B, st); else launch_transpose<float>(hin, f->dev, b->B, f->rows, f->rows, b->B, st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(x->ev_in[k], st));
-  if (f->name == "xfrc_applied") b->xfrc_on = 1;
-  if (f->name != "ctrl" && f->name != "qfrc_applied" && f->name != "xfrc_applied") return bump_epoch(b, st, false);      // stream-ordered with the edit
+  if (f == &b->fields[F_xfrc_applied]) b->xfrc_on = 1;
+  if (!(f->flags & DMC_FIELD_ACC_IN)) return bump_epoch(b, st, false);      // stream-ordered with the edit
   return 0;
 }
 extern "C" int dmc_batch_get_async(dmc_batch* b, int n, const char* const* names, void* hip_stream) {
@@ -981,6 +844,37 @@ extern "C" const void* dmc_batch_get_staged(dmc_batch* b, int i) {
   if (!b || !b->xfer || b->xfer->out_in_flight || i < 0 || (size_t)i >= b->xfer->pending.size()) { fail("no completed get holds that field"); return nullptr; }
   return (const char*)b->xfer->h_out + b->xfer->pending[i].second;
 }
+// (B, rows) doubles from the (rows, B) device array of T
+template <typename T>
+static int get_transposed(const dmc_batch* b, const Field* f, double* dst) {
+  std::vector<T> tmp((size_t)f->rows * b->B);
+  HIP_TRY(hipMemcpy(tmp.data(), f->dev, tmp.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (int k = 0; k < f->rows; k++) for (int e = 0; e < b->B; e++) dst[(size_t)e * f->rows + k] = tmp[(size_t)k * b->B + e];
+  return 0;
+}
+static int get_real(dmc_batch* b, Field* f, double* dst) {
+  const size_t n = (size_t)f->rows * b->B;
+  if (!n) return 0;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!get_in_flight(b)) {      // the pinned / device-transposed path, completed before returning
+    if (dmc_batch_get_async(b, 1, &f->name, nullptr)) return -2;
+    void* d = dst;
+    return dmc_batch_get_wait(b, 1, &d, 64);
+  }
+  return field_elem(b, f) == 8 ? get_transposed<double>(b, f, dst) : get_transposed<float>(b, f, dst);
+}
+static int set_real(dmc_batch* b, Field* f, const double* src) {
+  const size_t n = (size_t)f->rows * b->B;
+  if (!n) return 0;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipDeviceSynchronize());
+  // (inputs of the acceleration stage only, DMC_FIELD_ACC_IN, leave the stash epoch alone; every other field bumps it)
+  // the synchronous form of dmc_batch_set_async: pinned staging, device-side transposition, done before returning
+  if (dmc_batch_set_async(b, f->name, src, 64, nullptr)) return -2;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return 0;
+}
 extern "C" int dmc_batch_field_rows(const dmc_batch* b, const char* name, int* rows, int* is_int) {
   if (!b || !name) return fail("null argument");
   Field* f = find_field(const_cast<dmc_batch*>(b), name);
@@ -1001,10 +895,7 @@ extern "C" int dmc_batch_set(dmc_batch* b, const char* name, const double* src) 
   if (!f || f->is_int) return fail(std::string("unknown real field: ") + name);
   return set_real(b, f, src);
 }
-extern "C" int dmc_batch_get_int(dmc_batch* b, const char* name, int32_t* dst) {
-  if (!b || !name || !dst) return fail("null argument");
-  Field* f = find_field(b, name);
-  if (!f || !f->is_int) return fail(std::string("unknown int field: ") + name);
+static int get_int(dmc_batch* b, const Field* f, int32_t* dst) {
   const size_t n = (size_t)f->rows * b->B;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -1013,10 +904,7 @@ extern "C" int dmc_batch_get_int(dmc_batch* b, const char* name, int32_t* dst) {
   for (int k = 0; k < f->rows; k++) for (int e = 0; e < b->B; e++) dst[(size_t)e * f->rows + k] = tmp[(size_t)k * b->B + e];
   return 0;
 }
-extern "C" int dmc_batch_set_int(dmc_batch* b, const char* name, const int32_t* src) {
-  if (!b || !name || !src) return fail("null argument");
-  Field* f = find_field(b, name);
-  if (!f || !f->is_int) return fail(std::string("unknown int field: ") + name);
+static int set_int(dmc_batch* b, Field* f, const int32_t* src) {
   const size_t n = (size_t)f->rows * b->B;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -1025,11 +913,23 @@ extern "C" int dmc_batch_set_int(dmc_batch* b, const char* name, const int32_t* 
   HIP_TRY(hipMemcpy(f->dev, tmp.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
   return 0;
 }
+extern "C" int dmc_batch_get_int(dmc_batch* b, const char* name, int32_t* dst) {
+  if (!b || !name || !dst) return fail("null argument");
+  Field* f = find_field(b, name);
+  if (!f || !f->is_int) return fail(std::string("unknown int field: ") + name);
+  return get_int(b, f, dst);
+}
+extern "C" int dmc_batch_set_int(dmc_batch* b, const char* name, const int32_t* src) {
+  if (!b || !name || !src) return fail("null argument");
+  Field* f = find_field(b, name);
+  if (!f || !f->is_int) return fail(std::string("unknown int field: ") + name);
+  return set_int(b, f, src);
+}
 extern "C" void* dmc_batch_device_ptr(dmc_batch* b, const char* name) {
   if (!b || !name) { fail("null argument"); return nullptr; }
   Field* f = find_field(b, name);
   if (!f) { fail(std::string("unknown field: ") + name); return nullptr; }
-  if (f->name == "xfrc_applied") b->xfrc_on = 1;
+  if (f == &b->fields[F_xfrc_applied]) b->xfrc_on = 1;
   return f->dev;
 }
 extern "C" int dmc_batch_bind(dmc_batch* b, const char* name, void* device_ptr) {
@@ -1037,8 +937,10 @@ extern "C" int dmc_batch_bind(dmc_batch* b, const char* name, void* device_ptr) 
   Field* f = find_field(b, name);
   if (!f) return fail(std::string("unknown field: ") + name);
   f->dev = device_ptr ? device_ptr : f->owned;
-  if (f->name == "xfrc_applied") b->xfrc_on = 1;
-  if (f->name != "ctrl" && f->name != "qfrc_applied") { if (bump_epoch(b, 0, true)) return -2; }
+  const bool xfrc = f == &b->fields[F_xfrc_applied];
+  if (xfrc) b->xfrc_on = 1;
+  // (the one exception to DMC_FIELD_ACC_IN: binding xfrc_applied bumps the epoch, writing it does not)
+  if (!(f->flags & DMC_FIELD_ACC_IN) || xfrc) { if (bump_epoch(b, 0, true)) return -2; }
   return 0;
 }
 extern "C" int dmc_batch_invalidate(dmc_batch* b) {
@@ -1055,6 +957,81 @@ extern "C" int dmc_batch_set_output_mask(dmc_batch* b, int mask) {
   b->outmask = mask;
   return 0;
 }
+// ---- per-environment model deltas: world-fixed geoms with per-env pose / size ---------------------------------
+// The reference randomises scenery per episode by editing the MJCF and recompiling (soccer RandomizedPitch,
+// locomotion/soccer/pitch.py:612-690 through composer's initialize_episode_mjcf); a batch shares one compiled model,
+// so the geoms that differ between environments get their pose and size from a per-env array instead of the tables.
+static double geom_rbound_of(int type, const double* size) {
+  switch (type) {
+    case DMC_GEOM_SPHERE: return size[0];
+    case DMC_GEOM_CAPSULE: return size[0] + size[1];
+    case DMC_GEOM_CYLINDER: return sqrt(size[0]*size[0] + size[1]*size[1]);
+    case DMC_GEOM_ELLIPSOID: return std::max(size[0], std::max(size[1], size[2]));
+    case DMC_GEOM_BOX: return sqrt(size[0]*size[0] + size[1]*size[1] + size[2]*size[2]);
+    default: return 0;
+  }
+}
+extern "C" int dmc_batch_set_env_geoms(dmc_batch* b, int n, const int* geom_ids) {
+  if (!b || n < 1 || !geom_ids) return fail("null argument");
+  Field& f = b->fields[F_env_geom];
+  if (f.name) return fail("per-environment geoms were already declared for this batch");
+  const HostModel& m = b->model->hm;
+  std::vector<int> slot(m.ngeom, -1);
+  for (int k = 0; k < n; k++) {
+    const int g = geom_ids[k];
+    if (g < 0 || g >= m.ngeom) return fail("geom id out of range");
+    // world-fixed: on the worldbody, or on a jointless child of it whose frame is the world frame (PyMJCF attaches a
+    // static entity -- a goal -- as such a body; the per-environment row holds the geom's WORLD pose either way)
+    const int gb = m.geom_bodyid[g];
+    bool fixed = gb == 0;
+    if (!fixed && m.body_weldid[gb] == 0 && m.body_parentid[gb] == 0) {
+      const double* bp = &m.body_pos[3*gb]; const double* bq = &m.body_quat[4*gb];
+      fixed = bp[0] == 0 && bp[1] == 0 && bp[2] == 0 && bq[0] == 1 && bq[1] == 0 && bq[2] == 0 && bq[3] == 0;
+    }
+    if (!fixed) return fail("only world-fixed geoms (on the worldbody or on a jointless body at the world frame) can differ between environments");
+    if (slot[g] >= 0) return fail("geom listed twice");
+    slot[g] = k;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipDeviceSynchronize());
+  // (the field is declared last: a failed allocation leaves the batch as it was)
+  if (dev_alloc(b, &f.owned, (size_t)16 * n * b->B * b->elem, false, "per-environment geoms")) return -2;
+  if (dev_alloc(b, &b->d_eg_slot, sizeof(int) * m.ngeom, false, "per-environment geoms", slot.data())) { dev_free(b, &f.owned); return -2; }
+  f.name = "env_geom"; f.rows = 16*n; f.dev = f.owned;
+  // initial values: the model's own
+  std::vector<double> host((size_t)b->B * f.rows);
+  for (int k = 0; k < n; k++) {
+    const int g = geom_ids[k];
+    const double* q = &m.geom_quat[4*g];
+    double mat[9];
+    { const double w = q[0], x = q[1], y = q[2], z = q[3];
+      mat[0] = w*w + x*x - y*y - z*z; mat[4] = w*w - x*x + y*y - z*z; mat[8] = w*w - x*x - y*y + z*z;
+      mat[1] = 2*(x*y - w*z); mat[2] = 2*(x*z + w*y); mat[3] = 2*(x*y + w*z); mat[5] = 2*(y*z - w*x); mat[6] = 2*(x*z - w*y); mat[7] = 2*(y*z + w*x); }
+    double row[16];
+    for (int j = 0; j < 3; j++) row[j] = m.geom_pos[3*g + j];
+    for (int j = 0; j < 9; j++) row[3 + j] = mat[j];
+    for (int j = 0; j < 3; j++) row[12 + j] = m.geom_size[3*g + j];
+    row[15] = m.geom_rbound[g];
+    for (int e = 0; e < b->B; e++) for (int j = 0; j < 16; j++) host[(size_t)e * f.rows + 16*k + j] = row[j];
+  }
+  b->tb.opts.eg_slot = b->d_eg_slot; b->tb.opts.eg_n = n; b->tb.opts.eg_B = b->B;
+  if (bump_epoch(b, 0, true)) return -2;
+  return set_real(b, &f, host.data());
+}
+// rows of one geom slot from (pos, quat, size): what a caller writes into "env_geom" (host helper, no device work)
+extern "C" int dmc_env_geom_pack(int geom_type, const double* pos, const double* quat, const double* size, double* out16) {
+  if (!pos || !quat || !size || !out16) return fail("null argument");
+  const double n = sqrt(quat[0]*quat[0] + quat[1]*quat[1] + quat[2]*quat[2] + quat[3]*quat[3]);
+  if (!(n > 0)) return fail("zero quaternion");
+  const double w = quat[0]/n, x = quat[1]/n, y = quat[2]/n, z = quat[3]/n;
+  for (int j = 0; j < 3; j++) out16[j] = pos[j];
+  double* mat = out16 + 3;
+  mat[0] = w*w + x*x - y*y - z*z; mat[4] = w*w - x*x + y*y - z*z; mat[8] = w*w - x*x - y*y + z*z;
+  mat[1] = 2*(x*y - w*z); mat[2] = 2*(x*z + w*y); mat[3] = 2*(x*y + w*z); mat[5] = 2*(y*z - w*x); mat[6] = 2*(x*z - w*y); mat[7] = 2*(y*z + w*x);
+  for (int j = 0; j < 3; j++) out16[12 + j] = size[j];
+  out16[15] = geom_rbound_of(geom_type, size);
+  return 0;
+}
 extern "C" int dmc_batch_set_opt_int(dmc_batch* b, const char* name, int value) {
   if (!b || !name) return fail("null argument");
   StepOpts<double>& o = b->tb.opts;
@@ -1064,9 +1041,7 @@ extern "C" int dmc_batch_set_opt_int(dmc_batch* b, const char* name, int value) 
       const StepLayout& L = b->tb.L;
       HIP_TRY(hipSetDevice(b->device));
       const size_t nr = (size_t)std::max(1, L.n_keep) * b->B * b->elem, ni = (size_t)(L.n_si + 4) * b->B * sizeof(int);
-      HIP_TRY(hipMalloc(&b->d_stash_r, nr));
-      HIP_TRY(hipMalloc((void**)&b->d_stash_i, ni));
-      HIP_TRY(hipMemset(b->d_stash_i, 0, ni));
+      if (dev_alloc(b, &b->d_stash_i, ni, true, "stash") || dev_alloc(b, &b->d_stash_r, nr, false, "stash")) return -2;
     }
     b->stash_on = value ? 1 : 0;
     return 0;
@@ -1145,8 +1120,8 @@ extern "C" int dmc_batch_reset(dmc_batch* b, const uint8_t* env_mask, int keyfra
   const HostModel& m = b->model->hm;
   if (keyframe >= m.nkey) return fail("keyframe out of range");
   const int B = b->B;
-  auto reset_real = [&](const char* name, const double* init, int rows) -> int {
-    Field* f = find_field(b, name);
+  auto reset_real = [&](FieldId id, const double* init, int rows) -> int {
+    Field* f = &b->fields[id];
     if (!rows) return 0;
     std::vector<double> host((size_t)B * rows);
     if (env_mask) { if (get_real(b, f, host.data())) return -2; }
@@ -1156,15 +1131,15 @@ extern "C" int dmc_batch_reset(dmc_batch* b, const uint8_t* env_mask, int keyfra
   const double* q0 = keyframe >= 0 ? &m.key_qpos[(size_t)keyframe * m.nq] : m.qpos0.data();
   const double* v0 = keyframe >= 0 ? &m.key_qvel[(size_t)keyframe * m.nv] : nullptr;
   const double* c0 = keyframe >= 0 ? &m.key_ctrl[(size_t)keyframe * m.nu] : nullptr;
-  if (reset_real("qpos", q0, m.nq)) return -2;
-  if (reset_real("qvel", v0, m.nv)) return -2;
-  if (reset_real("ctrl", c0, m.nu)) return -2;
-  if (reset_real("qacc_warmstart", nullptr, m.nv)) return -2;
-  if (reset_real("qfrc_applied", nullptr, m.nv)) return -2;
-  if (b->xfrc_on && reset_real("xfrc_applied", nullptr, 6*m.nbody)) return -2;
+  if (reset_real(F_qpos, q0, m.nq)) return -2;
+  if (reset_real(F_qvel, v0, m.nv)) return -2;
+  if (reset_real(F_ctrl, c0, m.nu)) return -2;
+  if (reset_real(F_qacc_warmstart, nullptr, m.nv)) return -2;
+  if (reset_real(F_qfrc_applied, nullptr, m.nv)) return -2;
+  if (b->xfrc_on && reset_real(F_xfrc_applied, nullptr, 6*m.nbody)) return -2;
   // mj_resetDataKeyframe restores time, the activations and the mocap poses of the keyframe as well
-  if (reset_real("time", keyframe >= 0 ? &m.key_time[keyframe] : nullptr, 1)) return -2;
-  if (reset_real("act", keyframe >= 0 && m.na ? &m.key_act[(size_t)keyframe * m.na] : nullptr, m.na)) return -2;
+  if (reset_real(F_time, keyframe >= 0 ? &m.key_time[keyframe] : nullptr, 1)) return -2;
+  if (reset_real(F_act, keyframe >= 0 && m.na ? &m.key_act[(size_t)keyframe * m.na] : nullptr, m.na)) return -2;
   if (m.nmocap) {      // mj_resetData: the mocap poses start at the bodies' model poses
     std::vector<double> mp(3 * (size_t)m.nmocap), mq(4 * (size_t)m.nmocap);
     for (int i = 0; i < m.nbody; i++) if (m.body_mocapid[i] >= 0) {
@@ -1175,15 +1150,14 @@ extern "C" int dmc_batch_reset(dmc_batch* b, const uint8_t* env_mask, int keyfra
       std::copy(m.key_mpos.begin() + (size_t)keyframe * 3 * m.nmocap, m.key_mpos.begin() + (size_t)(keyframe + 1) * 3 * m.nmocap, mp.begin());
       std::copy(m.key_mquat.begin() + (size_t)keyframe * 4 * m.nmocap, m.key_mquat.begin() + (size_t)(keyframe + 1) * 4 * m.nmocap, mq.begin());
     }
-    if (reset_real("mocap_pos", mp.data(), 3*m.nmocap)) return -2;
-    if (reset_real("mocap_quat", mq.data(), 4*m.nmocap)) return -2;
+    if (reset_real(F_mocap_pos, mp.data(), 3*m.nmocap)) return -2;
+    if (reset_real(F_mocap_quat, mq.data(), 4*m.nmocap)) return -2;
   }
   // mj_resetData clears warnings as well
-  Field* w = find_field(b, "warning");
+  Field* w = &b->fields[F_warning];
   std::vector<int32_t> wh((size_t)B * DMC_NWARNING, 0);
-  if (env_mask) { if (dmc_batch_get_int(b, "warning", wh.data())) return -2; for (int e = 0; e < B; e++) if (env_mask[e]) for (int k = 0; k < DMC_NWARNING; k++) wh[(size_t)e * DMC_NWARNING + k] = 0; }
-  (void)w;
-  return dmc_batch_set_int(b, "warning", wh.data());
+  if (env_mask) { if (get_int(b, w, wh.data())) return -2; for (int e = 0; e < B; e++) if (env_mask[e]) for (int k = 0; k < DMC_NWARNING; k++) wh[(size_t)e * DMC_NWARNING + k] = 0; }
+  return set_int(b, w, wh.data());
 }
 
 extern "C" int dmc_batch_info(const dmc_batch* b, int* info) {
@@ -1239,17 +1213,23 @@ extern "C" int dmc_batch_time_steps(dmc_batch* b, int nstep, int legacy_step, in
 extern "C" int dmc_batch_debug_enable(dmc_batch* b, int n) {
   if (!b) return fail("null batch");
   HIP_TRY(hipSetDevice(b->device));
-  if (b->d_debug) { (void)hipFree(b->d_debug); b->d_debug = nullptr; }
-  if (b->d_debug_i) { (void)hipFree(b->d_debug_i); b->d_debug_i = nullptr; }
+  dev_free(b, &b->d_debug); dev_free(b, &b->d_debug_i);
   b->ndebug = 0;
   if (n <= 0) return 0;
   if (n > b->B) n = b->B;
   const StepLayout& L = b->tb.L;
-  HIP_TRY(hipMalloc(&b->d_debug, (size_t)(L.n_sr + L.n_gs) * n * b->elem));
-  HIP_TRY(hipMalloc((void**)&b->d_debug_i, (size_t)L.n_si * n * sizeof(int)));
-  HIP_TRY(hipMemset(b->d_debug, 0, (size_t)(L.n_sr + L.n_gs) * n * b->elem));
-  HIP_TRY(hipMemset(b->d_debug_i, 0, (size_t)L.n_si * n * sizeof(int)));
+  if (dev_alloc(b, &b->d_debug, (size_t)(L.n_sr + L.n_gs) * n * b->elem, true, "debug window") ||
+      dev_alloc(b, &b->d_debug_i, (size_t)L.n_si * n * sizeof(int), true, "debug window")) return -2;
   b->ndebug = n;
+  return 0;
+}
+// dst[i] = element (off + i, env) of the (rows, n) dump of T
+template <typename T>
+static int debug_column(const void* dump, int off, int cnt, int n, int env, double* dst, int* count) {
+  std::vector<T> tmp((size_t)cnt * n);
+  HIP_TRY(hipMemcpy(tmp.data(), (const T*)dump + (size_t)off * n, tmp.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (int i = 0; i < cnt; i++) dst[i] = tmp[(size_t)i * n + env];
+  *count = cnt;
   return 0;
 }
 extern "C" int dmc_batch_debug_get(dmc_batch* b, const char* scratch_name, int env, double* dst, int* count) {
@@ -1259,23 +1239,9 @@ extern "C" int dmc_batch_debug_get(dmc_batch* b, const char* scratch_name, int e
   if (!step_layout_find(&b->tb.L, scratch_name, &off, &cnt, &kind)) return fail(std::string("unknown scratch array: ") + scratch_name);
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipDeviceSynchronize());
-  const int n = b->ndebug;
-  const size_t total = (size_t)cnt * n;
-  if (kind) {
-    std::vector<int> tmp(total);
-    HIP_TRY(hipMemcpy(tmp.data(), b->d_debug_i + (size_t)off * n, total * sizeof(int), hipMemcpyDeviceToHost));
-    for (int i = 0; i < cnt; i++) dst[i] = tmp[(size_t)i * n + env];
-  } else if (b->precision == 64) {
-    std::vector<double> tmp(total);
-    HIP_TRY(hipMemcpy(tmp.data(), (double*)b->d_debug + (size_t)off * n, total * sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < cnt; i++) dst[i] = tmp[(size_t)i * n + env];
-  } else {
-    std::vector<float> tmp(total);
-    HIP_TRY(hipMemcpy(tmp.data(), (float*)b->d_debug + (size_t)off * n, total * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < cnt; i++) dst[i] = tmp[(size_t)i * n + env];
-  }
-  *count = cnt;
-  return 0;
+  if (kind) return debug_column<int>(b->d_debug_i, off, cnt, b->ndebug, env, dst, count);
+  return b->precision == 64 ? debug_column<double>(b->d_debug, off, cnt, b->ndebug, env, dst, count)
+                            : debug_column<float>(b->d_debug, off, cnt, b->ndebug, env, dst, count);
 }
 
 // ---- per-episode joint randomisation on the device -------------------------------------------------------------
@@ -1354,19 +1320,18 @@ extern "C" int dmc_batch_randomize_joints(dmc_batch* b, uint64_t seed, int32_t* 
   if (!b->d_rj_i) {
     std::vector<int> ji(3 * (size_t)std::max(1, nj));
     for (int j = 0; j < nj; j++) { ji[j] = m.jnt_type[j]; ji[nj + j] = m.jnt_qposadr[j]; ji[2*nj + j] = m.jnt_limited[j]; }
-    HIP_TRY(hipMalloc((void**)&b->d_rj_i, ji.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&b->d_rj_r, 2 * (size_t)std::max(1, nj) * sizeof(double)));
-    HIP_TRY(hipMemcpy(b->d_rj_i, ji.data(), ji.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (nj) HIP_TRY(hipMemcpy(b->d_rj_r, m.jnt_range.data(), 2 * (size_t)nj * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> jr(2 * (size_t)std::max(1, nj));
+    std::copy(m.jnt_range.begin(), m.jnt_range.begin() + 2 * (size_t)nj, jr.begin());
+    if (dev_alloc(b, &b->d_rj_r, jr.size() * sizeof(double), false, "joint ranges", jr.data()) ||
+        dev_alloc(b, &b->d_rj_i, ji.size() * sizeof(int), false, "joint ranges", ji.data())) return -2;
   }
   const dim3 grid((b->B + 255) / 256), block(256);
-  void* q = find_field(b, "qpos")->dev;
-  if (b->precision == 64)
-    hipLaunchKernelGGL(randomize_joints_kernel<double>, grid, block, 0, (hipStream_t)hip_stream, (double*)q, b->B, nj, (const int*)b->d_rj_i,
+  void* q = b->fields[F_qpos].dev;
+  auto run = [&](auto* qpos) {
+    hipLaunchKernelGGL(randomize_joints_kernel, grid, block, 0, (hipStream_t)hip_stream, qpos, b->B, nj, (const int*)b->d_rj_i,
                        (const double*)b->d_rj_r, (uint32_t)seed, (uint32_t)(seed >> 32), d_draw, d_env_mask, flags);
-  else
-    hipLaunchKernelGGL(randomize_joints_kernel<float>, grid, block, 0, (hipStream_t)hip_stream, (float*)q, b->B, nj, (const int*)b->d_rj_i,
-                       (const double*)b->d_rj_r, (uint32_t)seed, (uint32_t)(seed >> 32), d_draw, d_env_mask, flags);
+  };
+  if (b->precision == 64) run((double*)q); else run((float*)q);
   HIP_TRY(hipGetLastError());
   // qpos was edited behind the stashes' back
   return dmc_batch_invalidate_async(b, hip_stream);
@@ -1385,13 +1350,9 @@ extern "C" int dmc_batch_wave_trace(dmc_batch* b, int enable, int32_t* dst, int*
     return 0;
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (b->d_trace) { (void)hipFree(b->d_trace); b->d_trace = nullptr; }
+  dev_free(b, &b->d_trace);
   b->trace_launch = 0;
-  if (enable) {
-    HIP_TRY(hipMalloc((void**)&b->d_trace, (size_t)64 * n * sizeof(int)));
-    HIP_TRY(hipMemset(b->d_trace, 0, (size_t)64 * n * sizeof(int)));
-  }
-  return 0;
+  return enable ? dev_alloc(b, &b->d_trace, (size_t)64 * n * sizeof(int), true, "wave trace") : 0;
 }
 
 // ---- per-phase cycle profile (only meaningful in -DDMC_PROFILE builds) -----------
@@ -1401,11 +1362,9 @@ extern "C" int dmc_batch_prof_enable(dmc_batch* b, int enable) {
   if (enable) return fail("library built without DMC_PROFILE");
 #endif
   HIP_TRY(hipSetDevice(b->device));
-  if (b->d_prof) { (void)hipFree(b->d_prof); b->d_prof = nullptr; }
+  dev_free(b, &b->d_prof);
   if (!enable) return 0;
-  HIP_TRY(hipMalloc((void**)&b->d_prof, (size_t)32 * b->B * sizeof(long long)));
-  HIP_TRY(hipMemset(b->d_prof, 0, (size_t)32 * b->B * sizeof(long long)));
-  return 0;
+  return dev_alloc(b, &b->d_prof, (size_t)32 * b->B * sizeof(long long), true, "phase counters");
 }
 // dst: (PROF_N) mean cycles per env, accumulated since enable; returns PROF_N in *n
 extern "C" int dmc_batch_prof_get(dmc_batch* b, double* dst, int* n) {
@@ -1432,7 +1391,6 @@ struct dmc_camera {
   int tex_on, tex_filter, sky; float sky1[3], sky2[3];
   void* d_mat;      // CamMat<T>[ngeom] in the batch precision
   std::vector<double> mat_rgba_own;      // (ngeom, 4): a material record's own rgba, NaN where it has none
-  int f_gpos, f_gmat, f_xpos, f_xmat, f_com;      // field indices
 };
 template <typename T>
 static void cam_spec_to_dev(const dmc_camera_spec& s, int H, CamDev<T>* d) {
@@ -1476,8 +1434,6 @@ extern "C" int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* 
       c->matid[g] = opt->geom_matid[g];
     }
   }
-  c->f_gpos = b->index["geom_xpos"]; c->f_gmat = b->index["geom_xmat"]; c->f_xpos = b->index["xpos"];
-  c->f_xmat = b->index["xmat"]; c->f_com = b->index["subtree_com"];
   c->d_cams = nullptr; c->d_type = nullptr; c->d_skip = nullptr; c->d_color = nullptr;
   c->d_mat = nullptr; c->tex_on = 0; c->tex_filter = 0; c->sky = 0;
   hipError_t e = hipSetDevice(b->device);
@@ -1591,11 +1547,11 @@ template <typename T>
 static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void* seg, void* stream) {
   dmc_batch* b = c->b;
   CamArgs<T> a;
-  a.geom_xpos = (const T*)b->fields[c->f_gpos].dev; a.geom_xmat = (const T*)b->fields[c->f_gmat].dev;
-  a.xpos = (const T*)b->fields[c->f_xpos].dev; a.xmat = (const T*)b->fields[c->f_xmat].dev;
-  a.subtree_com = (const T*)b->fields[c->f_com].dev;
+  a.geom_xpos = (const T*)b->fields[F_geom_xpos].dev; a.geom_xmat = (const T*)b->fields[F_geom_xmat].dev;
+  a.xpos = (const T*)b->fields[F_xpos].dev; a.xmat = (const T*)b->fields[F_xmat].dev;
+  a.subtree_com = (const T*)b->fields[F_subtree_com].dev;
   a.geom_size = (const T*)b->d_mr + b->tb.L.mr_geom_size;
-  Field* eg = b->tb.opts.eg_n ? find_field(b, "env_geom") : nullptr;
+  const Field* eg = b->tb.opts.eg_n ? &b->fields[F_env_geom] : nullptr;
   a.eg_data = eg ? (const T*)eg->dev : nullptr; a.eg_slot = eg ? b->d_eg_slot : nullptr;
   a.geom_type = c->d_type; a.geom_skip = c->d_skip; a.geom_color = c->d_color;
   a.cams = (const CamDev<T>*)c->d_cams;

@@ -61,7 +61,12 @@ enum {
   OUT_ALL = 0x7fffffff
 };
 
-// SoA device arrays: element (k, env) of a field lives at base[k * B + env]
+// what a launch runs (the `mode` argument of the launch entries and of StepCore::run, which spell the values out):
+// Physics.step(nstep), mj_forward, mj_forward with actuation disabled, a rollout of nstep x nsub steps, mj_step1, mj_step2
+enum LaunchMode { MODE_STEP = 0, MODE_FORWARD = 1, MODE_FORWARD_NOACT = 2, MODE_ROLLOUT = 3, MODE_STEP1 = 4, MODE_STEP2 = 5 };
+
+// SoA device arrays: element (k, env) of a field lives at base[k * B + env]; the pointers of the data fields are filled
+// from DMC_DATA_*_FIELDS (dmc_model_layout.h: every field without DMC_FIELD_OPTS has the member of its name here)
 template <typename T>
 struct StepIO {
   int B;

@@ -119,14 +119,12 @@ int dmc_batch_forward(dmc_batch* b, int disable_actuation, void* hip_stream);
  * key_mpos, key_mquat of that keyframe. */
 int dmc_batch_reset(dmc_batch* b, const uint8_t* env_mask, int keyframe);
 
-/* Field access by mjData name ("qpos", "qvel", "act", "ctrl", "qacc_warmstart", "time",
- * "qfrc_applied", "xfrc_applied" (6 per body: Cartesian force, torque at the body COM; read by the kernel once it has been
- * written, bound or exposed through dmc_batch_device_ptr), "sensordata", "xpos", "xquat", "xmat", "xipos", "geom_xpos",
- * "geom_xmat", "site_xpos", "site_xmat", "subtree_com", "qacc", "actuator_force",
- * "qfrc_actuator", "qfrc_bias", "qfrc_constraint", "contact_dist", "contact_pos",
- * "contact_frame", "contact_force" (mj_contactForce per contact, valid after dmc_batch_forward;
- * wrapper/core.py:527-552), "cvel" (for mj_objectVelocity, wrapper/core.py:500-525); int32: "ncon", "nefc", "solver_iter", "warning",
- * "contact_geom1", "contact_geom2", "env_mode").  "env_mode" (one int per environment, default 0) overrides what a
+/* Field access by mjData name.  The fields, their rows per environment and which are int32 are the lists
+ * DMC_DATA_REAL_FIELDS / DMC_DATA_INT_FIELDS of dmc_model_layout.h (plus "env_geom" once dmc_batch_set_env_geoms declared
+ * it).  Of those that are not plain mjData arrays: "xfrc_applied" (6 per body: Cartesian force, torque at the body COM) is
+ * read by the kernel once it has been written, bound or exposed through dmc_batch_device_ptr; "contact_force" is
+ * mj_contactForce per contact, valid after dmc_batch_forward (wrapper/core.py:527-552); "cvel" is there for
+ * mj_objectVelocity (wrapper/core.py:500-525).  "env_mode" (one int per environment, default 0) overrides what a
  * dmc_batch_step / step1 / step2 launch does to that environment: 0 = step, 1 = mj_forward with actuation
  * disabled instead (an environment re-initialised under the reference's reset_context, rl/control.py:232-253,
  * while the rest of the batch steps), 2 = leave it untouched (also honoured by dmc_batch_forward: refresh only

@@ -133,6 +133,30 @@ enum { DMC_WARN_INERTIA = 0, DMC_WARN_CONTACTFULL = 1, DMC_WARN_CNSTRFULL = 2,
         * resolve (cylinders: tested as their enclosing capsules) came into contact range */
        DMC_WARN_COLLISION = 8, DMC_NWARNING = 9 };
 
+/* ---- the batch's data fields (mjData): X(name, count_expr, flags) --------
+ * The one list of what dmc_batch_get / set / bind know by name, in the order of the field ids: the C ABI's field
+ * table and its StepIO fill (dmc_api.hip), the host emulation (tests/emu) and dm_control_amd/_layout.py all expand or
+ * parse it.  Count expressions are rows per environment over nq nv nu na nbody ngeom nsite nsensordata nmocap nconmax;
+ * real fields are stored in the batch precision, int fields as int32.  Flags: */
+enum { DMC_FIELD_F64 = 1,     /* stored as fp64 whatever the batch precision */
+       DMC_FIELD_ACC_IN = 2,  /* an input of the acceleration stage only: a write leaves the stash epoch alone */
+       DMC_FIELD_OPTS = 4 };  /* no StepIO member: reaches the kernel through StepOpts */
+#define DMC_DATA_REAL_FIELDS(X) \
+  X(qpos, nq, 0) X(qvel, nv, 0) X(ctrl, nu, DMC_FIELD_ACC_IN) X(qacc_warmstart, nv, 0) \
+  X(qfrc_applied, nv, DMC_FIELD_ACC_IN) X(xfrc_applied, 6*nbody, DMC_FIELD_ACC_IN | DMC_FIELD_OPTS) \
+  X(time, 1, DMC_FIELD_F64) X(act, na, 0) \
+  X(mocap_pos, 3*nmocap, DMC_FIELD_OPTS) X(mocap_quat, 4*nmocap, DMC_FIELD_OPTS) \
+  X(sensordata, nsensordata, 0) X(xpos, 3*nbody, 0) X(xquat, 4*nbody, 0) X(xmat, 9*nbody, 0) \
+  X(xipos, 3*nbody, 0) X(geom_xpos, 3*ngeom, 0) X(geom_xmat, 9*ngeom, 0) \
+  X(site_xpos, 3*nsite, 0) X(site_xmat, 9*nsite, 0) X(subtree_com, 3*nbody, 0) \
+  X(qacc, nv, 0) X(actuator_force, nu, 0) X(qfrc_actuator, nv, 0) \
+  X(qfrc_bias, nv, 0) X(qfrc_constraint, nv, 0) \
+  X(contact_dist, nconmax, 0) X(contact_pos, 3*nconmax, 0) X(contact_frame, 9*nconmax, 0) \
+  X(contact_force, 6*nconmax, 0) X(cvel, 6*nbody, 0)
+#define DMC_DATA_INT_FIELDS(X) \
+  X(ncon, 1, 0) X(nefc, 1, 0) X(solver_iter, 1, 0) X(warning, DMC_NWARNING, 0) \
+  X(contact_geom1, nconmax, 0) X(contact_geom2, nconmax, 0) X(env_mode, 1, 0)
+
 #define DMC_MINVAL 1e-15
 #define DMC_MAXVAL 1e10
 #define DMC_MINMU  1e-5

@@ -73,40 +73,49 @@ void emu_set_env_geoms(void* h, int n, const int* ids, const double* data) {
   for (int k = 0; k < n; k++) e->eg_slot[ids[k]] = k;
   e->eg64.assign(data, data + 16*n); e->eg32.assign(data, data + 16*n);
 }
+// rows of every data field as the count expressions of DMC_DATA_*_FIELDS give them, reals then ints; returns how many
+int emu_field_rows(void* h, int* out) {
+  const StepDims& d = ((Emu*)h)->tb.L.d;
+  const int nq = d.nq, nv = d.nv, nu = d.nu, na = d.na, nbody = d.nbody, ngeom = d.ngeom, nsite = d.nsite,
+            nsensordata = d.nsensordata, nmocap = d.nmocap, nconmax = d.nconmax;
+  int k = 0;
+#define X(name, count, flags) out[k++] = count;
+  DMC_DATA_REAL_FIELDS(X) DMC_DATA_INT_FIELDS(X)
+#undef X
+  return k;
+}
 int emu_find(void* h, const char* name, int* off, int* cnt, int* kind) { return step_layout_find(&((Emu*)h)->tb.L, name, off, cnt, kind); }
 
 }  // extern "C"
 
 // io arrays are for ONE environment (B = 1).  prec: 64 or 32 (fp32 converts in/out).
 template <typename T>
-static void run_t(Emu* e, const T* mr, double** f, int** fi, int nstep, int legacy, int mode, double* dbg, int* dbgi) {
+static void run_t(Emu* e, const T* mr, double** f, int** fi, int nstep, int legacy, LaunchMode mode, double* dbg, int* dbgi) {
   const StepLayout& L = e->tb.L;
   StepOpts<T> o = step_opts_cast<T>(e->tb.opts);
   std::vector<T> s(L.n_sr, (T)0); std::vector<int> si(L.n_si, 0);
-  // field order matches tests/emu_lib.py
-  const int nb = L.d.nbody;
-  const int sizes[] = {L.d.nq, L.d.nv, L.d.nu, L.d.nv, L.d.nv, 1,
-                       L.d.nsensordata, 3*nb, 4*nb, 9*nb, 3*nb, 3*L.d.ngeom, 9*L.d.ngeom,
-                       3*L.d.nsite, 9*L.d.nsite, 3*nb, L.d.nv, L.d.nu, L.d.nv, L.d.nv, L.d.nv,
-                       L.d.nconmax, 3*L.d.nconmax, 9*L.d.nconmax, 6*L.d.nconmax, 6*nb, L.d.na};
-  const int NF = sizeof(sizes)/sizeof(int);
-  std::vector<std::vector<T>> buf(NF);
-  for (int k = 0; k < NF; k++) { buf[k].resize(sizes[k] + 1); for (int i = 0; i < sizes[k]; i++) buf[k][i] = (T)f[k][i]; }
-  std::vector<T> dbuf(L.n_sr + L.n_gs); std::vector<int> dibuf(L.n_si);
+  // f / fi: one array per entry of DMC_DATA_REAL_FIELDS / DMC_DATA_INT_FIELDS, in that order (tests/emu_lib.py builds them
+  // from the same lists).  Reals are converted to T and back, fp64 fields (time) and ints are used in place; the fields
+  // that reach the kernel through StepOpts are set by emu_set_xfrc / emu_set_mocap, their arrays here are ignored.
+  int rows[64];
+  emu_field_rows(e, rows);
+  std::vector<std::vector<T>> buf;
   StepIO<T> io;
   io.B = 1;
-  io.qpos = buf[0].data(); io.qvel = buf[1].data(); io.ctrl = buf[2].data(); io.qacc_warmstart = buf[3].data();
-  io.qfrc_applied = buf[4].data(); double tm = f[5][0]; io.time = &tm; io.prof = nullptr; io.ctrl_seq = nullptr; io.qpos_seq = nullptr; io.qvel_seq = nullptr; io.sensor_seq = nullptr;
-  io.sensordata = buf[6].data(); io.xpos = buf[7].data(); io.xquat = buf[8].data(); io.xmat = buf[9].data();
-  io.xipos = buf[10].data(); io.geom_xpos = buf[11].data(); io.geom_xmat = buf[12].data();
-  io.site_xpos = buf[13].data(); io.site_xmat = buf[14].data(); io.subtree_com = buf[15].data();
-  io.qacc = buf[16].data(); io.actuator_force = buf[17].data(); io.qfrc_actuator = buf[18].data();
-  io.qfrc_bias = buf[19].data(); io.qfrc_constraint = buf[20].data();
-  io.contact_dist = buf[21].data(); io.contact_pos = buf[22].data(); io.contact_frame = buf[23].data();
-  io.contact_force = buf[24].data(); io.cvel = buf[25].data(); io.act = buf[26].data();
-  io.ncon = fi[0]; io.nefc = fi[1]; io.solver_iter = fi[2]; io.warning = fi[3]; io.contact_geom1 = fi[4]; io.contact_geom2 = fi[5];
+  int k = 0;      // (a field's storage stays where it is when `buf` grows)
+#define X(name, count, flags) buf.emplace_back(f[k], f[k] + rows[k]); buf[k].push_back((T)0); \
+  if constexpr (!((flags) & DMC_FIELD_OPTS)) { if constexpr ((flags) & DMC_FIELD_F64) io.name = f[k]; else io.name = buf[k].data(); } \
+  k++;
+  DMC_DATA_REAL_FIELDS(X)
+#undef X
+  k = 0;
+#define X(name, count, flags) io.name = fi[k++];
+  DMC_DATA_INT_FIELDS(X)
+#undef X
+  std::vector<T> dbuf(L.n_sr + L.n_gs); std::vector<int> dibuf(L.n_si);
+  io.prof = nullptr; io.ctrl_seq = nullptr; io.qpos_seq = nullptr; io.qvel_seq = nullptr; io.sensor_seq = nullptr;
   io.debug = dbg ? dbuf.data() : nullptr; io.debug_i = dibuf.data(); io.ndebug = dbg ? 1 : 0;
-  io.env_mode = nullptr; io.work = nullptr; io.cost = nullptr; io.order = nullptr; io.trace = nullptr; io.trace_slot = 0;
+  io.work = nullptr; io.cost = nullptr; io.order = nullptr; io.trace = nullptr; io.trace_slot = 0;
   if (!e->xfrc64.empty()) { o.xfrc = sizeof(T) == 8 ? (const void*)e->xfrc64.data() : (const void*)e->xfrc32.data(); o.xfrc_B = 1; }
   if (L.d.nmocap) {
     if (e->mpos64.empty()) {      // mj_resetData: the model poses
@@ -127,15 +136,18 @@ static void run_t(Emu* e, const T* mr, double** f, int** fi, int nstep, int lega
   DynLayoutSrc ls; ls.p = &L;
   StepCore<T, 1> core(ls, o, e->tb.mi.data(), mr, e->tb.mc.data(), s.data(), si.data(), 0);
   core.run(io, 0, nstep, legacy, mode, OUT_ALL, 1);
-  for (int k = 0; k < NF; k++) for (int i = 0; i < sizes[k]; i++) f[k][i] = (double)buf[k][i];
-  f[5][0] = tm;
+  k = 0;
+#define X(name, count, flags) if (!((flags) & DMC_FIELD_F64)) for (int i = 0; i < rows[k]; i++) f[k][i] = (double)buf[k][i]; \
+  k++;
+  DMC_DATA_REAL_FIELDS(X)
+#undef X
   if (dbg) { for (int i = 0; i < L.n_sr + L.n_gs; i++) dbg[i] = (double)dbuf[i]; for (int i = 0; i < L.n_si; i++) dbgi[i] = dibuf[i]; }
 }
 extern "C" {
 int emu_run(void* h, int prec, double** f, int** fi, int nstep, int legacy, int mode, double* dbg, int* dbgi) {
   Emu* e = (Emu*)h;
-  if (prec == 64) run_t<double>(e, e->tb.mr.data(), f, fi, nstep, legacy, mode, dbg, dbgi);
-  else run_t<float>(e, e->mr32.data(), f, fi, nstep, legacy, mode, dbg, dbgi);
+  if (prec == 64) run_t<double>(e, e->tb.mr.data(), f, fi, nstep, legacy, (LaunchMode)mode, dbg, dbgi);
+  else run_t<float>(e, e->mr32.data(), f, fi, nstep, legacy, (LaunchMode)mode, dbg, dbgi);
   return 0;
 }
 }

@@ -5,17 +5,16 @@ import subprocess
 
 import numpy as np
 
+from dm_control_amd import _layout
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, 'emu', 'emu.cpp')
 _LIB = os.path.join(_HERE, 'emu', 'libemu.so')
 _lib = None
 
-FIELDS = ['qpos', 'qvel', 'ctrl', 'qacc_warmstart', 'qfrc_applied', 'time',
-          'sensordata', 'xpos', 'xquat', 'xmat', 'xipos', 'geom_xpos', 'geom_xmat',
-          'site_xpos', 'site_xmat', 'subtree_com', 'qacc', 'actuator_force',
-          'qfrc_actuator', 'qfrc_bias', 'qfrc_constraint',
-          'contact_dist', 'contact_pos', 'contact_frame', 'contact_force', 'cvel', 'act']
-IFIELDS = ['ncon', 'nefc', 'solver_iter', 'warning', 'contact_geom1', 'contact_geom2']
+# the data fields of include/dmc_model_layout.h, in its order: emu_run takes one array per field, in this order
+FIELDS = [n for n, _ in _layout.DATA_REAL_FIELDS]
+IFIELDS = [n for n, _ in _layout.DATA_INT_FIELDS]
 
 
 def lib():
@@ -48,6 +47,7 @@ def lib():
     L.emu_set_mocap.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.emu_set_env_geoms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.emu_dims.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.emu_field_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.emu_tree_tables.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 5
     L.emu_find.argtypes = [ctypes.c_void_p, ctypes.c_char_p] + [ctypes.POINTER(ctypes.c_int)] * 3
     L.emu_run.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -70,19 +70,19 @@ class EmuPhysics:
     self.n_sr, self.n_si, self.nconmax, self.njmax = [int(x) for x in dims[:4]]
     self.kmax = int(dims[6])
     m = compiled
-    nb = m.nbody
-    sizes = [m.nq, m.nv, m.nu, m.nv, m.nv, 1, m.nsensordata, 3*nb, 4*nb, 9*nb, 3*nb,
-             3*m.ngeom, 9*m.ngeom, 3*m.nsite, 9*m.nsite, 3*nb, m.nv, m.nu, m.nv, m.nv, m.nv,
-             self.nconmax, 3*self.nconmax, 9*self.nconmax, 6*self.nconmax, 6*nb, m.na]
-    self.f = {n: np.zeros(max(s, 1)) for n, s in zip(FIELDS, sizes)}
-    self._sizes = dict(zip(FIELDS, sizes))
-    self.fi = {'ncon': np.zeros(1, np.int32), 'nefc': np.zeros(1, np.int32),
-               'solver_iter': np.zeros(1, np.int32), 'warning': np.zeros(9, np.int32),
-               'contact_geom1': np.zeros(self.nconmax, np.int32),
-               'contact_geom2': np.zeros(self.nconmax, np.int32)}
+    self._sizes = _layout.data_field_counts(m, self.nconmax)
+    self.f = {n: np.zeros(max(self._sizes[n], 1)) for n in FIELDS}
+    self.fi = {n: np.zeros(self._sizes[n], np.int32) for n in IFIELDS}
     self.f['qpos'][:m.nq] = m.qpos0
     self.dbg = np.zeros(self.n_sr)
     self.dbgi = np.zeros(self.n_si, np.int32)
+
+  def field_rows(self):
+    """{name: rows} of every data field as the C side evaluates the header's count expressions."""
+    out = np.zeros(64, np.int32)
+    n = lib().emu_field_rows(self.h, out.ctypes.data)
+    assert n == len(FIELDS + IFIELDS)
+    return dict(zip(FIELDS + IFIELDS, (int(x) for x in out[:n])))
 
   def tree_tables(self):
     """StepDims::treemax models: dict(treemax, ntreetri, ntree, tree0, tree1, tri (i, j) pairs, trim)."""

@@ -6,6 +6,7 @@ It lets the host stack (Physics facade, named indexing, Environment, every suite
 product never imports it and still fails loudly without a GPU."""
 import numpy as np
 
+from dm_control_amd import _layout
 from oracle.oracle import OracleModel, OraclePhysics
 
 _NWARN = 9
@@ -23,13 +24,9 @@ class OracleBatch:
     self._om = OracleModel(model)
     self._envs = [OraclePhysics(self._om) for _ in range(self.batch_size)]
     self.nconmax = nconmax or 16
-    m = model
-    nb = m.nbody
-    self._rows = dict(qpos=m.nq, qvel=m.nv, act=m.na, ctrl=m.nu, qacc_warmstart=m.nv, qfrc_applied=m.nv, xfrc_applied=6*nb, time=1,
-                      sensordata=m.nsensordata, xpos=3*nb, xquat=4*nb, xmat=9*nb, xipos=3*nb, geom_xpos=3*m.ngeom,
-                      geom_xmat=9*m.ngeom, site_xpos=3*m.nsite, site_xmat=9*m.nsite, subtree_com=3*nb, qacc=m.nv,
-                      actuator_force=m.nu, qfrc_actuator=m.nv, qfrc_bias=m.nv, qfrc_constraint=m.nv, cvel=6*nb,
-                      mocap_pos=3*m.nmocap, mocap_quat=4*m.nmocap)
+    # rows of the real data fields (include/dmc_model_layout.h); the contact arrays are assembled in get()
+    self._rows = {n: r for n, r in _layout.data_field_counts(model, self.nconmax).items()
+                  if n in dict(_layout.DATA_REAL_FIELDS) and not n.startswith('contact_')}
 
   def close(self):
     self._envs = []
