@@ -1,0 +1,415 @@
+"""What the two host facades (`physics.Physics` / `_Data` and `mujoco_api.MjModel` / `MjData`) share: the mjData arrays the
+fused kernel never stores, derived from the device's kinematics, and MuJoCo's state layout.
+
+numpy only, no facade state, every function pure: `c` is a compiled `mjcf_compiler.Model`, everything else arrives as
+arrays (or as a `get(name, *shape)` reader of them).  The functions both facades call (`joint_frames`, `tendons`,
+`object_velocity`, the row helpers) take arbitrary leading batch axes -- `(..., n, 3)` is one environment or `B` of them,
+and the batched result equals the per-environment ones to the bit.  The derivations only `MjData` serves (`mass_matrix`,
+`passive`, `act_dot`, `subtree_vel`) take one environment.
+
+This module never imports `BatchedPhysics`: tests swap that name in each facade separately, so `create_batch` takes the
+class from its caller.
+"""
+import numpy as np
+
+from dm_control_amd import mjcf_compiler
+
+C = mjcf_compiler.C
+MINVAL = C['DMC_MINVAL']
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tables
+# ---------------------------------------------------------------------------------------------------------------------
+# the mjData arrays a caller writes and the next launch reads (`time` is an input too: each facade handles it itself)
+INPUT_FIELDS = ('qpos', 'qvel', 'act', 'ctrl', 'qacc_warmstart', 'qfrc_applied', 'xfrc_applied', 'mocap_pos', 'mocap_quat')
+# model arrays tasks may rewrite between episodes; changes are pushed to the device tables in place before the next launch
+MUTABLE_MODEL_FIELDS = ('dof_damping', 'jnt_stiffness', 'jnt_range', 'jnt_margin', 'qpos_spring', 'site_pos', 'site_quat',
+                        'site_size', 'actuator_ctrlrange', 'actuator_forcerange', 'wrap_prm', 'body_pos', 'body_quat',
+                        # geom frames / sizes as tasks rewrite them (suite/reacher.py:88-94, suite/fish.py:150-154: the
+                        # target geom); like MuJoCo, nothing derived at compile time (inertias, geom_rbound) follows
+                        'geom_pos', 'geom_quat', 'geom_size')
+# contact capacities tried, in order, when the caller names none: MuJoCo sizes its contact buffer from an arena (any
+# number of contacts a model can produce fits), a drop-in user never sets `nconmax` -- so the facades ask for a generous
+# cap first and settle for less only where the model's scratch would not fit in LDS.  (The throughput path,
+# BatchedPhysics / suite.load, keeps its tuned per-model caps: suite/common.py DEFAULT_CAPS.)
+AUTO_NCONMAX = (64, 48, 32, 0)
+# mjtState bits (mujoco 3.x) in the order mj_getState concatenates them: (mjSTATE_<name>, mjData field)
+STATE_FIELDS = (('TIME', 'time'), ('QPOS', 'qpos'), ('QVEL', 'qvel'), ('ACT', 'act'), ('WARMSTART', 'qacc_warmstart'),
+                ('CTRL', 'ctrl'), ('QFRC_APPLIED', 'qfrc_applied'), ('XFRC_APPLIED', 'xfrc_applied'),
+                ('EQ_ACTIVE', 'eq_active'), ('MOCAP_POS', 'mocap_pos'), ('MOCAP_QUAT', 'mocap_quat'), ('USERDATA', None),
+                ('PLUGIN', None))
+NSTATE = len(STATE_FIELDS)
+# qpos / qvel entries per joint type (free, ball, slide, hinge)
+JNT_NQ = {0: 7, 1: 4, 2: 1, 3: 1}
+JNT_NV = {0: 6, 1: 3, 2: 1, 3: 1}
+# mj_objectVelocity's object kinds, by name and by mjtObj: (name table, position field, orientation field | None: the
+# inertial frame of a body, xquat * body_iquat)
+OBJECT_KINDS = {'body': ('body', 'xipos', None), 'xbody': ('body', 'xpos', 'xmat'), 'geom': ('geom', 'geom_xpos', 'geom_xmat'),
+                'site': ('site', 'site_xpos', 'site_xmat')}
+OBJECT_KINDS.update({C['DMC_OBJ_' + k.upper()]: v for k, v in list(OBJECT_KINDS.items())})
+
+
+def state_parts(c, sig):
+  """[(mjSTATE name, mjData field | None, size)] of the components `sig` selects, in bit order.  (The callers check `sig`:
+  each raises its own error type.)"""
+  nm = int(getattr(c, 'nmocap', 0))
+  sizes = {'TIME': 1, 'QPOS': c.nq, 'QVEL': c.nv, 'ACT': c.na, 'WARMSTART': c.nv, 'CTRL': c.nu, 'QFRC_APPLIED': c.nv,
+           'XFRC_APPLIED': 6 * c.nbody, 'EQ_ACTIVE': len(getattr(c, 'eq_active0', ())), 'MOCAP_POS': 3 * nm,
+           'MOCAP_QUAT': 4 * nm, 'USERDATA': 0, 'PLUGIN': 0}      # (no user data / plugins in a compiled Model)
+  return [(n, f, int(sizes[n])) for i, (n, f) in enumerate(STATE_FIELDS) if int(sig) & (1 << i)]
+
+
+def joint_spans(c):
+  """(first qpos entry, qpos entries, first dof, dofs) per joint."""
+  return (c.jnt_qposadr, [JNT_NQ[int(t)] for t in c.jnt_type], c.jnt_dofadr, [JNT_NV[int(t)] for t in c.jnt_type])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the batch: contact capacity fallback, the xfrc_applied rule, contact records
+# ---------------------------------------------------------------------------------------------------------------------
+def create_batch(factory, model, batch_size, **kw):
+  """`factory(model, batch_size, nconmax=cap, **kw)` for the first cap of AUTO_NCONMAX whose scratch fits."""
+  for cap in AUTO_NCONMAX:
+    try:
+      return factory(model, batch_size, nconmax=cap, **kw)
+    except Exception as e:      # pylint: disable=broad-except
+      if cap == AUTO_NCONMAX[-1] or 'does not fit' not in str(e):
+        raise
+
+
+def send_xfrc(state, a):
+  """Whether the `xfrc_applied` array `a` goes to the batch whose owner keeps its marks in the dict `state` (a batch that
+  was just created: `{}`).  Uploading xfrc_applied switches the kernel's external-force path on for good (6 nbody reals
+  per environment per step), and a mere READ of the array makes a facade consider it for upload: all-zero forces are only
+  sent once a non-zero one has been, i.e. when there is something to clear."""
+  if not np.any(a) and not state.get('_xfrc_sent', False):
+    return False
+  state['_xfrc_sent'] = True
+  return True
+
+
+def fill_contacts(buf, n, get):
+  """The first `n` records of the structured array `buf` from one environment's `contact_*` device fields."""
+  for col, width in (('geom1', 1), ('geom2', 1), ('dist', 1), ('pos', 3), ('frame', 9)):
+    buf[col][:n] = np.asarray(get('contact_' + col)).reshape(-1, *((width,) if width > 1 else ()))[:n]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# row helpers: quaternions (..., 4), vectors (..., 3)
+# ---------------------------------------------------------------------------------------------------------------------
+def cross(a, b):
+  return np.stack([a[..., 1]*b[..., 2] - a[..., 2]*b[..., 1], a[..., 2]*b[..., 0] - a[..., 0]*b[..., 2],
+                   a[..., 0]*b[..., 1] - a[..., 1]*b[..., 0]], axis=-1)
+
+
+def quat_mul_rows(a, b):
+  w1, x1, y1, z1 = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+  w2, x2, y2, z2 = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+  return np.stack([w1*w2 - x1*x2 - y1*y2 - z1*z2, w1*x2 + x1*w2 + y1*z2 - z1*y2,
+                   w1*y2 - x1*z2 + y1*w2 + z1*x2, w1*z2 + x1*y2 - y1*x2 + z1*w2], axis=-1)
+
+
+def quat_to_mat_rows(q):
+  """(..., 4) -> (..., 9), row-major."""
+  w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+  return np.stack([w*w + x*x - y*y - z*z, 2*(x*y - w*z), 2*(x*z + w*y),
+                   2*(x*y + w*z), w*w - x*x + y*y - z*z, 2*(y*z - w*x),
+                   2*(x*z - w*y), 2*(y*z + w*x), w*w - x*x - y*y + z*z], axis=-1)
+
+
+def _mats(q):
+  return quat_to_mat_rows(q).reshape(q.shape[:-1] + (3, 3))
+
+
+def _rot(R, v):
+  return np.einsum('...ij,...j->...i', R, v)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-model plans: index tables that depend on the model's structure only, built once and kept with the compiled model
+# ---------------------------------------------------------------------------------------------------------------------
+PLAN_ATTR = '_host_plans'
+
+
+def _plan(c, build):
+  plans = c.__dict__.setdefault(PLAN_ATTR, {})
+  name = build.__name__
+  if name not in plans:
+    plans[name] = build(c)
+  return plans[name]
+
+
+def _joint_plan(c):
+  """The joints grouped by their rank counted from the LAST joint of their body (pass r of joint_frames handles every
+  rank-r joint of the model at once)."""
+  rank = np.zeros(c.njnt, dtype=np.int64)
+  for b in range(c.nbody):
+    j0, jn = int(c.body_jntadr[b]), int(c.body_jntnum[b])
+    for k in range(jn):
+      rank[j0 + k] = jn - 1 - k
+  typ = np.asarray(c.jnt_type, dtype=np.int64)
+  passes = []
+  for r in range(int(rank.max()) + 1 if c.njnt else 0):
+    js = np.nonzero(rank == r)[0]
+    passes.append({'j': js, 'b': np.asarray(c.jnt_bodyid, dtype=np.int64)[js], 't': typ[js],
+                   'qa': np.asarray(c.jnt_qposadr, dtype=np.int64)[js]})
+  return passes
+
+
+def _dof_plan(c):
+  nv = c.nv
+  kind = np.zeros(nv, dtype=np.int64)      # 0: world axis (free translation), 1: a column of the body's xmat, 2: the joint's xaxis
+  col, jnt, body, rot, fixed_anchor = (np.zeros(nv, dtype=np.int64) for _ in range(5))
+  for j in range(c.njnt):
+    d, t, b = int(c.jnt_dofadr[j]), int(c.jnt_type[j]), int(c.jnt_bodyid[j])
+    n = JNT_NV[t]
+    jnt[d:d + n], body[d:d + n] = j, b
+    if t == 0:
+      kind[d:d + 3], col[d:d + 3] = 0, np.arange(3)
+      kind[d + 3:d + 6], col[d + 3:d + 6], rot[d + 3:d + 6], fixed_anchor[d + 3:d + 6] = 1, np.arange(3), 1, 1
+    elif t == 1:
+      kind[d:d + 3], col[d:d + 3], rot[d:d + 3] = 1, np.arange(3), 1
+    else:
+      kind[d], rot[d] = 2, int(t == 3)
+  return dict(kind=kind, col=col, jnt=jnt, body=body, rot=rot.astype(bool), free_rot=fixed_anchor.astype(bool))
+
+
+def _body_dofmask(c):
+  """mask[b, k]: body b is moved by dof k (k's body is b or an ancestor of b)."""
+  anc = np.zeros((c.nbody, c.nv), dtype=bool)
+  for b in range(1, c.nbody):
+    anc[b] = anc[int(c.body_parentid[b])]
+    d0, dn = int(c.body_dofadr[b]), int(c.body_dofnum[b])
+    if dn:
+      anc[b, d0:d0 + dn] = True
+  return anc
+
+
+def _subtree(c):
+  """sub[r, b]: b is in the subtree rooted at r."""
+  sub = np.zeros((c.nbody, c.nbody), dtype=bool)
+  for b in range(c.nbody):
+    a = b
+    while True:
+      sub[a, b] = True
+      if a == 0:
+        break
+      a = int(c.body_parentid[a])
+  return sub
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# derivations both facades serve
+# ---------------------------------------------------------------------------------------------------------------------
+def joint_frames(c, qpos, xpos, xquat):
+  """mjData.xanchor / xaxis as (anchor, axis), each (..., njnt, 3), from qpos (..., nq) and the device's body frames xpos
+  (..., nbody, 3) / xquat (..., nbody, 4).  mj_kinematics takes each joint's anchor and axis in the body frame accumulated
+  BEFORE that joint moves it; here the walk runs the other way, from the body's FINAL frame back through its joints: a
+  hinge or ball rotation leaves its own anchor and axis where they were, a slide moves the frame along its axis.  One
+  vectorised pass per joint rank within a body (at most three in the suite models), over all environments at once.  (A
+  mocap body has no joints; its children start from its device frame like any other.)"""
+  qpos = np.asarray(qpos, dtype=np.float64)
+  lead = qpos.shape[:-1]
+  anchor, axis = np.zeros(lead + (c.njnt, 3)), np.zeros(lead + (c.njnt, 3))
+  if not c.njnt:
+    return anchor, axis
+  pos, quat = np.array(xpos, dtype=np.float64), np.array(xquat, dtype=np.float64)      # current frame per body
+  jaxis, jpos = np.asarray(c.jnt_axis, dtype=np.float64), np.asarray(c.jnt_pos, dtype=np.float64)
+  q0 = np.asarray(c.qpos0, dtype=np.float64)
+  for ps in _plan(c, _joint_plan):
+    js, bs, ts, qa = ps['j'], ps['b'], ps['t'], ps['qa']
+    R = _mats(quat[..., bs, :])
+    ax = _rot(R, jaxis[js])
+    an = pos[..., bs, :] + _rot(R, jpos[js])
+    free, ball, slide, hinge = ts == 0, ts == 1, ts == 2, ts == 3
+    if free.any():
+      k = np.nonzero(free)[0]
+      an[..., k, :] = np.stack([qpos[..., qa[k]], qpos[..., qa[k] + 1], qpos[..., qa[k] + 2]], axis=-1)
+      ax[..., k, :] = jaxis[js[k]]
+    if slide.any():
+      k = np.nonzero(slide)[0]
+      shift = ax[..., k, :] * (qpos[..., qa[k]] - q0[qa[k]])[..., None]
+      an[..., k, :] -= shift
+      pos[..., bs[k], :] -= shift
+    rot = hinge | ball
+    if rot.any():
+      k = np.nonzero(rot)[0]
+      qloc = np.zeros(lead + (k.size, 4))
+      kh = hinge[k]
+      if kh.any():
+        ang = (qpos[..., qa[k[kh]]] - q0[qa[k[kh]]]) / 2
+        qloc[..., kh, 0] = np.cos(ang)
+        qloc[..., kh, 1:] = jaxis[js[k[kh]]] * np.sin(ang)[..., None]
+      kb = ~kh
+      if kb.any():
+        qb = np.stack([qpos[..., qa[k[kb]] + i] for i in range(4)], axis=-1)
+        qloc[..., kb, :] = qb / np.linalg.norm(qb, axis=-1, keepdims=True)
+      qprev = quat_mul_rows(quat[..., bs[k], :], qloc * np.array([1.0, -1, -1, -1]))
+      quat[..., bs[k], :] = qprev
+      Rp = _mats(qprev)
+      pos[..., bs[k], :] = an[..., k, :] - _rot(Rp, jpos[js[k]])
+      if kb.any():      # (a ball joint turns its own nominal axis: mjData.xaxis is the axis BEFORE the joint acts)
+        ax[..., k[kb], :] = _rot(Rp[..., kb, :, :], jaxis[js[k[kb]]])
+    anchor[..., js, :], axis[..., js, :] = an, ax
+  return anchor, axis
+
+
+def spatial_tendons(c):
+  """Ids of the tendons that run through sites (`tendons` needs the site positions and body velocities for these only)."""
+  return [t for t in range(c.ntendon) if c.tendon_num[t] and c.wrap_type[c.tendon_adr[t]] != C['DMC_WRAP_JOINT']]
+
+
+def tendons(c, qpos, qvel, site_xpos=None, cvel=None, subtree_com=None):
+  """mjData.ten_length / ten_velocity / wrap_xpos (mj_tendon, mj_fwdVelocity: `ten_velocity = ten_J qvel`) as (length
+  (..., ntendon), velocity (..., ntendon), wrap_xpos (..., nwrap, 6)) -- the kernel re-derives the few tendon lengths
+  where it needs them and stores none.  Fixed tendons: the coefficient-weighted sum of joint coordinates / velocities;
+  site-to-site spatial tendons: the segment lengths, and their rates from the sites' velocities (com-based `cvel` of the
+  body, moved to the site).  `site_xpos (..., nsite, 3)`, `cvel (..., nbody, 6)` and `subtree_com (..., nbody, 3)` are read
+  only if the model has `spatial_tendons`."""
+  qpos, qvel = np.asarray(qpos, dtype=np.float64), np.asarray(qvel, dtype=np.float64)
+  lead, nt = qpos.shape[:-1], c.ntendon
+  length, velocity, wrap = np.zeros(lead + (nt,)), np.zeros(lead + (nt,)), np.zeros(lead + (c.nwrap, 6))
+  spatial = spatial_tendons(c)
+
+  def point(w):
+    sid = int(c.wrap_objid[w])
+    b = int(c.site_bodyid[sid])
+    pos = site_xpos[..., sid, :]
+    return pos, cvel[..., b, 3:] + np.cross(cvel[..., b, :3], pos - subtree_com[..., c.body_rootid[b], :])
+  for t in range(nt):
+    w0, wn = int(c.tendon_adr[t]), int(c.tendon_num[t])
+    if t not in spatial:
+      for w in range(w0, w0 + wn):
+        j = int(c.wrap_objid[w])
+        length[..., t] += c.wrap_prm[w] * qpos[..., c.jnt_qposadr[j]]
+        velocity[..., t] += c.wrap_prm[w] * qvel[..., c.jnt_dofadr[j]]
+      continue
+    for w in range(w0, w0 + wn - 1):
+      (p0, v0), (p1, v1) = point(w), point(w + 1)
+      wrap[..., w, :3], wrap[..., w, 3:] = p0, p1
+      dif = p1 - p0
+      n = np.linalg.norm(dif, axis=-1)
+      length[..., t] += n
+      ok = n > MINVAL
+      velocity[ok, t] += np.einsum('ek,ek->e', dif[ok] / n[ok, None], (v1 - v0)[ok])
+  return length, velocity, wrap
+
+
+def object_velocity(c, kind, objid, get, local):
+  """mj_objectVelocity (wrapper/core.py:500-525): the 6D velocity of a body / xbody / geom / site as (angular, linear),
+  each (..., 3), in the world frame or (`local`) the object's own, from the com-based `cvel` of its body.  `kind`: a key of
+  OBJECT_KINDS; `get(field, *shape)` reads an mjData array as (..., *shape)."""
+  rows, posf, matf = OBJECT_KINDS[kind]
+  body = int(objid if rows == 'body' else c.geom_bodyid[objid] if rows == 'geom' else c.site_bodyid[objid])
+  n = {'body': c.nbody, 'geom': c.ngeom, 'site': c.nsite}[rows]
+  pos = get(posf, n, 3)[..., objid, :]
+  if matf is None:
+    mat = _mats(quat_mul_rows(get('xquat', c.nbody, 4)[..., objid, :], np.asarray(c.body_iquat[objid], dtype=np.float64)))
+  else:
+    mat = get(matf, n, 3, 3)[..., objid, :, :]
+  cvel = get('cvel', c.nbody, 6)[..., body, :]
+  com = get('subtree_com', c.nbody, 3)[..., int(c.body_rootid[body]), :]
+  ang = cvel[..., :3]
+  lin = cvel[..., 3:] - np.cross(pos - com, ang)
+  if local:
+    ang, lin = np.einsum('...ij,...i->...j', mat, ang), np.einsum('...ij,...i->...j', mat, lin)
+  return ang, lin
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# derivations only MjData serves (one environment)
+# ---------------------------------------------------------------------------------------------------------------------
+def mass_matrix(c, xpos, xmat, xipos, ximat, xanchor, xaxis):
+  """Dense joint-space inertia M(q) (what mj_crb leaves in mjData.M) from world-frame body Jacobians:
+  M = sum_b m_b Jp_b' Jp_b + Jr_b' (R_b I_b R_b') Jr_b + diag(dof_armature)."""
+  nv, nb = c.nv, c.nbody
+  p = _plan(c, _dof_plan)
+  R = np.asarray(xmat, dtype=np.float64).reshape(nb, 3, 3)
+  axis = np.where((p['kind'] == 2)[:, None], xaxis[p['jnt']], R[p['body'], :, p['col']])
+  axis = np.where((p['kind'] == 0)[:, None], np.eye(3)[p['col']], axis)
+  anchor = np.where(p['free_rot'][:, None], xpos[p['body']], xanchor[p['jnt']])
+  rot = p['rot']
+  mask = _plan(c, _body_dofmask)                             # (nb, nv)
+  r = xipos[:, None, :] - anchor[None, :, :]                 # (nb, nv, 3)
+  jp = np.where(rot[None, :, None], cross(np.broadcast_to(axis[None, :, :], r.shape), r), axis[None, :, :]) * mask[:, :, None]
+  jr = np.where(rot[None, :, None], axis[None, :, :], 0.0) * mask[:, :, None]
+  Ri = np.asarray(ximat, dtype=np.float64).reshape(nb, 3, 3)
+  jl = np.einsum('bji,bkj->bki', Ri, jr)                     # angular Jacobian in the inertial frame: (nb, nv, 3)
+  M = np.einsum('b,bki,bli->kl', np.asarray(c.body_mass, dtype=np.float64), jp, jp)
+  M += np.einsum('bki,bi,bli->kl', jl, np.asarray(c.body_inertia, dtype=np.float64), jl)
+  M[np.diag_indices(nv)] += np.asarray(c.dof_armature, dtype=np.float64)
+  return M
+
+
+def passive(c, qpos, qvel):
+  """mjData.qfrc_passive (mj_passive): joint springs and dampers, fixed-tendon springs and dampers.  Fluid forces and
+  ball / free joint springs are computed on the device only: a model that has them is refused here rather than served a
+  partial sum."""
+  if float(c.opt.density) or float(c.opt.viscosity):
+    raise NotImplementedError('mjData.qfrc_passive of a model with fluid forces is not derived on the host')
+  flags = int(c.opt.disableflags)
+  out = np.zeros(c.nv)
+  if not flags & C['DMC_DSBL_DAMPER']:
+    out -= np.asarray(c.dof_damping, dtype=np.float64) * qvel
+  if not flags & C['DMC_DSBL_SPRING']:
+    for j in range(c.njnt):
+      k = float(c.jnt_stiffness[j])
+      if not k:
+        continue
+      if c.jnt_type[j] not in (2, 3):
+        raise NotImplementedError('mjData.qfrc_passive with a spring on a ball / free joint is not derived on the host')
+      out[c.jnt_dofadr[j]] -= k * (qpos[c.jnt_qposadr[j]] - c.qpos_spring[c.jnt_qposadr[j]])
+  for t in range(c.ntendon):
+    ks, kd = float(c.tendon_stiffness[t]), float(c.tendon_damping[t])
+    if not (ks or kd):
+      continue
+    w0, wn = int(c.tendon_adr[t]), int(c.tendon_num[t])
+    js = [int(c.wrap_objid[w]) for w in range(w0, w0 + wn)]
+    coef = np.asarray(c.wrap_prm[w0:w0 + wn], dtype=np.float64)
+    length = float(coef @ qpos[np.asarray(c.jnt_qposadr)[js]])
+    vel = float(coef @ qvel[np.asarray(c.jnt_dofadr)[js]])
+    f = 0.0
+    if ks and not flags & C['DMC_DSBL_SPRING']:
+      f -= ks * (length - float(c.tendon_lengthspring[t]))
+    if kd and not flags & C['DMC_DSBL_DAMPER']:
+      f -= kd * vel
+    out[np.asarray(c.jnt_dofadr)[js]] += coef * f
+  return out
+
+
+def act_dot(c, actadr, ctrl, act):
+  """mjData.act_dot (mj_fwdActuation): integrator `ctrl`, filter `(ctrl - act) / tau`; filterexact has the same rate.
+  `actadr`: mjModel.actuator_actadr."""
+  out = np.zeros(c.na)
+  for i in range(c.nu):
+    if actadr[i] < 0:
+      continue
+    u = ctrl[i]
+    if c.actuator_ctrllimited[i] and not int(c.opt.disableflags) & C['DMC_DSBL_CLAMPCTRL']:
+      u = min(max(u, c.actuator_ctrlrange[i, 0]), c.actuator_ctrlrange[i, 1])
+    if int(c.actuator_dyntype[i]) == C['DMC_DYN_INTEGRATOR']:
+      out[actadr[i]] = u
+    else:
+      out[actadr[i]] = (u - act[actadr[i]]) / max(MINVAL, c.actuator_dynprm[i, 0])
+  if int(c.opt.disableflags) & C['DMC_DSBL_ACTUATION']:
+    out[:] = 0
+  return out
+
+
+def subtree_vel(c, cvel, subtree_com, xipos, ximat=None):
+  """mj_subtreeVel as (subtree_linvel, subtree_angmom | None without `ximat`): linear velocity of every subtree's centre
+  of mass and its angular momentum about it, from the device's com-based body velocities."""
+  nb = c.nbody
+  mass = np.asarray(c.body_mass, dtype=np.float64)
+  sub = _plan(c, _subtree).astype(np.float64)                     # (root, body)
+  ang = cvel[:, :3]
+  lin = cvel[:, 3:] + cross(ang, xipos - subtree_com[np.asarray(c.body_rootid)])      # velocity of each body's own COM
+  msub = np.maximum(sub @ mass, MINVAL)
+  vsub = (sub @ (mass[:, None] * lin)) / msub[:, None]
+  if ximat is None:
+    return vsub, None
+  R = ximat.reshape(nb, 3, 3)
+  spin = np.einsum('bij,bj,bkj,bk->bi', R, np.asarray(c.body_inertia, dtype=np.float64), R, ang)
+  # sum_b [I w + m (x - X) x (v - V)] = sum_b [I w + m x x v] - M X x V   (X, V: the subtree's centre of mass and its velocity)
+  own = spin + mass[:, None] * cross(xipos, lin)
+  return vsub, sub @ own - msub[:, None] * cross(subtree_com, vsub)

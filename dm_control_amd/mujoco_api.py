@@ -28,7 +28,8 @@ every array).  Here every array handed out is ONE host ndarray for the life of t
   * after every launch, every array that has been handed out is rewritten in place from the device -- device outputs by
     one batched read, and the mjData arrays the fused kernel keeps on chip and never stores (`ximat xanchor xaxis M qM qLD
     qLDiagInv energy subtree_linvel subtree_angmom cam_x* light_x* ten_length ten_velocity wrap_xpos act_dot`) derived on the
-    host from the device's kinematics;
+    host from the device's kinematics (`host_data`: the derivations and the state layout shared with `physics.Physics`;
+    `_derive` here only knows which handed-out arrays to refresh);
   * model arrays are the compiled model's own ndarrays, all writable: before a launch the model blob is re-packed and
     compared with what the batch was created from -- options and constants the batch can follow in place go through
     `dmc_batch_set_opt_* / dmc_batch_set_model_real`, anything else rebuilds the batch from the edited model (the input
@@ -48,6 +49,7 @@ import pickle
 import numpy as np
 
 from dm_control_amd import _layout
+from dm_control_amd import host_data
 from dm_control_amd import mjcf_compiler
 from dm_control_amd.batch import BatchedPhysics      # (tests swap this name for the oracle stand-in)
 
@@ -132,8 +134,7 @@ mjtTimer = _enum('mjtTimer', _seq('mjTIMER_', ['STEP', 'FORWARD', 'INVERSE', 'PO
                                                'POS_PROJECT', 'COL_BROAD', 'COL_NARROW'], 'mjNTIMER'))
 mjtConstraint = _enum('mjtConstraint', _seq('mjCNSTR_', ['EQUALITY', 'FRICTION_DOF', 'FRICTION_TENDON', 'LIMIT_JOINT', 'LIMIT_TENDON',
                                                          'CONTACT_FRICTIONLESS', 'CONTACT_PYRAMIDAL', 'CONTACT_ELLIPTIC']))
-_STATE_NAMES = ['TIME', 'QPOS', 'QVEL', 'ACT', 'WARMSTART', 'CTRL', 'QFRC_APPLIED', 'XFRC_APPLIED', 'EQ_ACTIVE', 'MOCAP_POS',
-                'MOCAP_QUAT', 'USERDATA', 'PLUGIN']
+_STATE_NAMES = [n for n, _ in host_data.STATE_FIELDS]
 _SB = {n: 1 << i for i, n in enumerate(_STATE_NAMES)}
 _SB['PHYSICS'] = _SB['QPOS'] | _SB['QVEL'] | _SB['ACT']
 _SB['FULLPHYSICS'] = _SB['TIME'] | _SB['PHYSICS'] | _SB['PLUGIN']
@@ -367,23 +368,6 @@ def _build_extras(c):
   dyn = np.asarray(c.actuator_dyntype, dtype=np.int64)
   x['actuator_actnum'] = (dyn != 0).astype(np.int32)
   x['actuator_actadr'] = np.where(dyn != 0, np.cumsum(dyn != 0) - 1, -1).astype(np.int32)
-  # body c is moved by dof k iff k's body is c or an ancestor of c
-  anc = np.zeros((c.nbody, nv), dtype=bool)
-  for b in range(1, c.nbody):
-    anc[b] = anc[int(c.body_parentid[b])]
-    d0, dn = int(c.body_dofadr[b]), int(c.body_dofnum[b])
-    if dn:
-      anc[b, d0:d0 + dn] = True
-  x['body_dofmask'] = anc
-  sub = np.zeros((c.nbody, c.nbody), dtype=bool)      # sub[r, b]: b is in the subtree rooted at r
-  for b in range(c.nbody):
-    a = b
-    while True:
-      sub[a, b] = True
-      if a == 0:
-        break
-      a = int(c.body_parentid[a])
-  x['subtree'] = sub
   frames = xpos0, xquat0, com0 = _world_frames_at_qpos0(c)
   # (one derivation for the facade and the ray-cast cameras: mjcf_compiler.frame_constants)
   x['cam_pos0'], x['cam_poscom0'], x['cam_mat0'] = mjcf_compiler.frame_constants(
@@ -580,6 +564,7 @@ class MjModel(metaclass=_ModelMeta):
   def __copy__(self):
     c = _copy.deepcopy(self._c)
     c.__dict__.pop('_mj_extras', None)
+    c.__dict__.pop(host_data.PLAN_ATTR, None)
     return MjModel._wrap(c)
 
   def __deepcopy__(self, memo):
@@ -630,7 +615,7 @@ _MJB_MAGIC = b'DMCMJB02'      # 02: the compiled model carries the texture array
 
 def _dump_mjb(m):
   c = m._c
-  keep = {k: v for k, v in c.__dict__.items() if k not in ('_mj_extras', '_mj_vis', '_mj_xml')}
+  keep = {k: v for k, v in c.__dict__.items() if k not in ('_mj_extras', '_mj_vis', '_mj_xml', host_data.PLAN_ATTR)}
   clone = object.__new__(type(c))
   clone.__dict__.update(keep)
   return _MJB_MAGIC + pickle.dumps(clone, protocol=4)
@@ -747,7 +732,7 @@ def mj_id2name(m, type_, id_):
 # ---------------------------------------------------------------------------------------------------------------------
 # MjData
 # ---------------------------------------------------------------------------------------------------------------------
-_IN = ('qpos', 'qvel', 'act', 'ctrl', 'qacc_warmstart', 'qfrc_applied', 'xfrc_applied', 'mocap_pos', 'mocap_quat')
+_IN = host_data.INPUT_FIELDS
 _OUT = ('sensordata', 'xpos', 'xquat', 'xmat', 'xipos', 'geom_xpos', 'geom_xmat', 'site_xpos', 'site_xmat', 'subtree_com', 'qacc',
         'actuator_force', 'qfrc_actuator', 'qfrc_bias', 'qfrc_constraint', 'cvel')
 _DERIVED = ('ximat', 'xanchor', 'xaxis', 'cam_xpos', 'cam_xmat', 'light_xpos', 'light_xdir', 'ten_length', 'ten_velocity', 'wrap_xpos',
@@ -771,7 +756,6 @@ _CONTACT_DTYPE = np.dtype([('dist', np.float64), ('pos', np.float64, 3), ('frame
                            ('solimp', np.float64, 5), ('mu', np.float64), ('H', np.float64, 36), ('dim', np.int32),
                            ('geom1', np.int32), ('geom2', np.int32), ('geom', np.int32, 2), ('flex', np.int32, 2),
                            ('elem', np.int32, 2), ('vert', np.int32, 2), ('exclude', np.int32), ('efc_address', np.int32)])
-_AUTO_NCONMAX = (64, 48, 32, 0)      # as the Physics facade: generous contact capacity first, whatever fits in LDS
 
 
 def _size(m, s):
@@ -923,24 +907,14 @@ class MjData(metaclass=_DataMeta):
       src.eq_active0 = np.asarray(self._arrays['eq_active'], dtype=np.int64)
     else:
       src = c
-    err = None
-    for cap in _AUTO_NCONMAX:
-      try:
-        batch = BatchedPhysics(src, 1, device_id=0, precision=64, nconmax=cap)
-        break
-      except Exception as e:      # pylint: disable=broad-except
-        err = e
-        if cap == 0 or 'does not fit' not in str(e):
-          raise
-    else:
-      raise err
+    batch = host_data.create_batch(BatchedPhysics, src, 1, device_id=0, precision=64)
     old, self._batch = self._batch, batch
     self._nconmax = int(batch.info().get('nconmax', 0)) or 16
     self._pushed = tuple(a.copy() for a in self._packed_model())
     self._fingerprint = self._model_fingerprint()
     if carry is not None:
       for name, a in carry.items():
-        if name == 'xfrc_applied' and not a.any():
+        if name == 'xfrc_applied' and not host_data.send_xfrc({}, a):
           continue
         batch.set(name, a.reshape(1, -1))
     if old is not None and hasattr(old, 'close'):
@@ -1031,8 +1005,6 @@ class MjData(metaclass=_DataMeta):
   _OPT_INT = ('disableflags', 'iterations', 'ls_iterations', 'noslip_iterations')
   _OPT_REAL = {'opt_timestep': 'timestep', 'opt_gravity_x': 'gravity_x', 'opt_gravity_y': 'gravity_y', 'opt_gravity_z': 'gravity_z',
                'opt_tolerance': 'tolerance', 'opt_ls_tolerance': 'ls_tolerance', 'opt_noslip_tolerance': 'noslip_tolerance'}
-  _MUTABLE = ('dof_damping', 'jnt_stiffness', 'jnt_range', 'jnt_margin', 'qpos_spring', 'site_pos', 'site_quat', 'site_size',
-              'actuator_ctrlrange', 'actuator_forcerange', 'wrap_prm', 'body_pos', 'body_quat', 'geom_pos', 'geom_quat', 'geom_size')
 
   def _model_fingerprint(self):
     """Every number the model blob is made of, flat (one concatenate: this runs before every launch)."""
@@ -1092,7 +1064,7 @@ class MjData(metaclass=_DataMeta):
         for name, expr in _layout.REAL_FIELDS:
           n = _layout.field_count(expr, sizes)
           if n and not same[off:off + n].all():
-            if name not in self._MUTABLE:
+            if name not in host_data.MUTABLE_MODEL_FIELDS:
               rebuild = True
               break
             touched.append(name)
@@ -1120,10 +1092,8 @@ class MjData(metaclass=_DataMeta):
         continue
       dev = self._shadow[name]
       if not np.array_equal(a, dev, equal_nan=True):
-        if name == 'xfrc_applied' and not a.any() and not getattr(self, '_xfrc_sent', False):
+        if name == 'xfrc_applied' and not host_data.send_xfrc(vars(self), a):
           continue
-        if name == 'xfrc_applied':
-          self._xfrc_sent = True
         self._batch.set(name, a.reshape(1, -1))
         self._shadow[name] = a.copy()
         changed = True
@@ -1155,12 +1125,8 @@ class MjData(metaclass=_DataMeta):
       buf[...] = np.zeros((), dtype=_CONTACT_DTYPE)
       n = self.ncon
       if n:
-        buf['geom1'][:n] = np.asarray(b.get('contact_geom1')).ravel()[:n]
-        buf['geom2'][:n] = np.asarray(b.get('contact_geom2')).ravel()[:n]
+        host_data.fill_contacts(buf, n, b.get)
         buf['geom'][:n, 0], buf['geom'][:n, 1] = buf['geom1'][:n], buf['geom2'][:n]
-        buf['dist'][:n] = np.asarray(b.get('contact_dist')).ravel()[:n]
-        buf['pos'][:n] = np.asarray(b.get('contact_pos')).reshape(-1, 3)[:n]
-        buf['frame'][:n] = np.asarray(b.get('contact_frame')).reshape(-1, 9)[:n]
         c = self._model._c
         buf['dim'][:n] = np.maximum(c.geom_condim[buf['geom1'][:n]], c.geom_condim[buf['geom2'][:n]])
         buf['exclude'][:n] = 0
@@ -1279,10 +1245,8 @@ class MjData(metaclass=_DataMeta):
   def _restore(self, snap):
     b = self._batch
     for n, a in snap['inputs'].items():
-      if n == 'xfrc_applied' and not a.any():
+      if n == 'xfrc_applied' and not host_data.send_xfrc(vars(self), a):
         continue
-      if n == 'xfrc_applied':
-        self._xfrc_sent = True
       b.set(n, a.reshape(1, -1))
     b.set('time', np.array([[snap['time']]]))
     self._pull_inputs()
@@ -1333,141 +1297,6 @@ def _unpickle_data(model, snap):
 # ---------------------------------------------------------------------------------------------------------------------
 # host-side derivations of the mjData arrays the kernel keeps on chip
 # ---------------------------------------------------------------------------------------------------------------------
-def _cross(a, b):
-  return np.stack([a[..., 1]*b[..., 2] - a[..., 2]*b[..., 1], a[..., 2]*b[..., 0] - a[..., 0]*b[..., 2],
-                   a[..., 0]*b[..., 1] - a[..., 1]*b[..., 0]], axis=-1)
-
-
-def _joint_plan(c):
-  """Per model: the joints grouped by their rank counted from the LAST joint of their body (pass r of joint_frames
-  handles every rank-r joint of the model at once)."""
-  x = _extras(c)
-  plan = x.get('_joint_plan')
-  if plan is None:
-    rank = np.zeros(c.njnt, dtype=np.int64)
-    for b in range(c.nbody):
-      j0, jn = int(c.body_jntadr[b]), int(c.body_jntnum[b])
-      for k in range(jn):
-        rank[j0 + k] = jn - 1 - k
-    typ = np.asarray(c.jnt_type, dtype=np.int64)
-    passes = []
-    for r in range(int(rank.max()) + 1 if c.njnt else 0):
-      js = np.nonzero(rank == r)[0]
-      passes.append({'j': js, 'b': np.asarray(c.jnt_bodyid, dtype=np.int64)[js], 't': typ[js],
-                     'qa': np.asarray(c.jnt_qposadr, dtype=np.int64)[js]})
-    plan = x['_joint_plan'] = passes
-  return plan
-
-
-def joint_frames(c, qpos, xpos, xquat, mocap_pos=None, mocap_quat=None):
-  """mjData.xanchor / xaxis.  mj_kinematics takes each joint's anchor and axis in the body frame accumulated BEFORE that
-  joint moves it; here the walk runs the other way, from the body's FINAL frame (the device's xpos / xquat) back through
-  its joints: a hinge or ball rotation leaves its own anchor and axis where they were, a slide moves the frame along its
-  axis.  One vectorised pass per joint rank within a body (at most three in the suite models)."""
-  del mocap_pos, mocap_quat      # (a mocap body has no joints; its children start from its device frame like any other)
-  anchor, axis = np.zeros((c.njnt, 3)), np.zeros((c.njnt, 3))
-  if not c.njnt:
-    return anchor, axis
-  pos, quat = np.array(xpos, dtype=np.float64), np.array(xquat, dtype=np.float64)      # current frame per body
-  jaxis, jpos = np.asarray(c.jnt_axis, dtype=np.float64), np.asarray(c.jnt_pos, dtype=np.float64)
-  q0 = np.asarray(c.qpos0, dtype=np.float64)
-  for ps in _joint_plan(c):
-    js, bs, ts, qa = ps['j'], ps['b'], ps['t'], ps['qa']
-    R = _quat_to_mat_rows(quat[bs]).reshape(-1, 3, 3)
-    ax = np.einsum('nij,nj->ni', R, jaxis[js])
-    an = pos[bs] + np.einsum('nij,nj->ni', R, jpos[js])
-    free, ball, slide, hinge = ts == 0, ts == 1, ts == 2, ts == 3
-    if free.any():
-      k = np.nonzero(free)[0]
-      an[k] = np.stack([qpos[qa[k]], qpos[qa[k] + 1], qpos[qa[k] + 2]], axis=1)
-      ax[k] = jaxis[js[k]]
-    if slide.any():
-      k = np.nonzero(slide)[0]
-      shift = ax[k] * (qpos[qa[k]] - q0[qa[k]])[:, None]
-      an[k] -= shift
-      pos[bs[k]] -= shift
-    rot = hinge | ball
-    if rot.any():
-      k = np.nonzero(rot)[0]
-      qloc = np.zeros((k.size, 4))
-      kh = hinge[k]
-      if kh.any():
-        ang = (qpos[qa[k[kh]]] - q0[qa[k[kh]]]) / 2
-        qloc[kh, 0] = np.cos(ang)
-        qloc[kh, 1:] = jaxis[js[k[kh]]] * np.sin(ang)[:, None]
-      kb = ~kh
-      if kb.any():
-        qb = np.stack([qpos[qa[k[kb]] + i] for i in range(4)], axis=1)
-        qloc[kb] = qb / np.linalg.norm(qb, axis=1, keepdims=True)
-      qprev = _quat_mul_rows(quat[bs[k]], qloc * np.array([1.0, -1, -1, -1]))
-      quat[bs[k]] = qprev
-      Rp = _quat_to_mat_rows(qprev).reshape(-1, 3, 3)
-      pos[bs[k]] = an[k] - np.einsum('nij,nj->ni', Rp, jpos[js[k]])
-      if kb.any():      # (a ball joint turns its own nominal axis: mjData.xaxis is the axis BEFORE the joint acts)
-        ax[k[kb]] = np.einsum('nij,nj->ni', Rp[kb], jaxis[js[k[kb]]])
-    anchor[js], axis[js] = an, ax
-  return anchor, axis
-
-
-def _quat_mul_rows(a, b):
-  w1, x1, y1, z1 = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
-  w2, x2, y2, z2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
-  return np.stack([w1*w2 - x1*x2 - y1*y2 - z1*z2, w1*x2 + x1*w2 + y1*z2 - z1*y2,
-                   w1*y2 - x1*z2 + y1*w2 + z1*x2, w1*z2 + x1*y2 - y1*x2 + z1*w2], axis=1)
-
-
-def _quat_to_mat_rows(q):
-  w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-  return np.stack([w*w + x*x - y*y - z*z, 2*(x*y - w*z), 2*(x*z + w*y),
-                   2*(x*y + w*z), w*w - x*x + y*y - z*z, 2*(y*z - w*x),
-                   2*(x*z - w*y), 2*(y*z + w*x), w*w - x*x - y*y + z*z], axis=1)
-
-
-def _dof_plan(c):
-  x = _extras(c)
-  plan = x.get('_dof_plan')
-  if plan is None:
-    nv = c.nv
-    kind = np.zeros(nv, dtype=np.int64)      # 0: world axis (free translation), 1: a column of the body's xmat, 2: the joint's xaxis
-    col, jnt, body, rot, fixed_anchor = (np.zeros(nv, dtype=np.int64) for _ in range(5))
-    for j in range(c.njnt):
-      d, t, b = int(c.jnt_dofadr[j]), int(c.jnt_type[j]), int(c.jnt_bodyid[j])
-      n = {0: 6, 1: 3}.get(t, 1)
-      jnt[d:d + n], body[d:d + n] = j, b
-      if t == 0:
-        kind[d:d + 3], col[d:d + 3] = 0, np.arange(3)
-        kind[d + 3:d + 6], col[d + 3:d + 6], rot[d + 3:d + 6], fixed_anchor[d + 3:d + 6] = 1, np.arange(3), 1, 1
-      elif t == 1:
-        kind[d:d + 3], col[d:d + 3], rot[d:d + 3] = 1, np.arange(3), 1
-      else:
-        kind[d], rot[d] = 2, int(t == 3)
-    plan = x['_dof_plan'] = dict(kind=kind, col=col, jnt=jnt, body=body, rot=rot.astype(bool), free_rot=fixed_anchor.astype(bool))
-  return plan
-
-
-def mass_matrix(c, xpos, xmat, xipos, ximat, xanchor, xaxis):
-  """Dense joint-space inertia M(q) (what mj_crb leaves in mjData.M) from world-frame body Jacobians:
-  M = sum_b m_b Jp_b' Jp_b + Jr_b' (R_b I_b R_b') Jr_b + diag(dof_armature)."""
-  nv, nb = c.nv, c.nbody
-  x = _extras(c)
-  p = _dof_plan(c)
-  R = np.asarray(xmat, dtype=np.float64).reshape(nb, 3, 3)
-  axis = np.where((p['kind'] == 2)[:, None], xaxis[p['jnt']], R[p['body'], :, p['col']])
-  axis = np.where((p['kind'] == 0)[:, None], np.eye(3)[p['col']], axis)
-  anchor = np.where(p['free_rot'][:, None], xpos[p['body']], xanchor[p['jnt']])
-  rot = p['rot']
-  mask = x['body_dofmask']                                   # (nb, nv)
-  r = xipos[:, None, :] - anchor[None, :, :]                 # (nb, nv, 3)
-  jp = np.where(rot[None, :, None], _cross(np.broadcast_to(axis[None, :, :], r.shape), r), axis[None, :, :]) * mask[:, :, None]
-  jr = np.where(rot[None, :, None], axis[None, :, :], 0.0) * mask[:, :, None]
-  Ri = np.asarray(ximat, dtype=np.float64).reshape(nb, 3, 3)
-  jl = np.einsum('bji,bkj->bki', Ri, jr)                     # angular Jacobian in the inertial frame: (nb, nv, 3)
-  M = np.einsum('b,bki,bli->kl', np.asarray(c.body_mass, dtype=np.float64), jp, jp)
-  M += np.einsum('bki,bi,bli->kl', jl, np.asarray(c.body_inertia, dtype=np.float64), jl)
-  M[np.diag_indices(nv)] += np.asarray(c.dof_armature, dtype=np.float64)
-  return M
-
-
 def _derive(d, names):
   c, A = d._model._c, d._arrays
   x = _extras(c)
@@ -1477,6 +1306,8 @@ def _derive(d, names):
 
   def dev(n, *shape):      # a device array: the handed-out copy if there is one (it was just refreshed)
     return A[n].reshape(shape) if n in A and n in _OUT else get(n, *shape)
+  state = lambda n: d._shadow[n].ravel()      # an input array: what the device holds
+  put = lambda n, val: np.copyto(A[n], val) if n in A and val is not None else None
   nb = c.nbody
   heavy = need & {'M', 'qM', 'qLD', 'qLDiagInv', 'energy'}
   frames = need & {'xanchor', 'xaxis'} or heavy
@@ -1485,39 +1316,37 @@ def _derive(d, names):
     xpos, xquat = dev('xpos', nb, 3), dev('xquat', nb, 4)
   ximat = None
   if 'ximat' in need or heavy or 'subtree_angmom' in need:
-    ximat = _quat_to_mat_rows(_quat_mul_rows(xquat, np.asarray(c.body_iquat, dtype=np.float64).reshape(nb, 4)))
-    if 'ximat' in A:
-      np.copyto(A['ximat'], ximat)
+    ximat = host_data.quat_to_mat_rows(host_data.quat_mul_rows(xquat, np.asarray(c.body_iquat, dtype=np.float64).reshape(nb, 4)))
+    put('ximat', ximat)
   if frames:
-    nm = int(getattr(c, 'nmocap', 0))
-    anchor, axis = joint_frames(c, d._shadow['qpos'].ravel(), xpos, xquat,
-                                d._shadow['mocap_pos'].reshape(nm, 3) if nm else None,
-                                d._shadow['mocap_quat'].reshape(nm, 4) if nm else None)
-    if 'xanchor' in A:
-      np.copyto(A['xanchor'], anchor)
-    if 'xaxis' in A:
-      np.copyto(A['xaxis'], axis)
+    anchor, axis = host_data.joint_frames(c, state('qpos'), xpos, xquat)
+    put('xanchor', anchor)
+    put('xaxis', axis)
   for pre, n, bodyid, pos in (('cam', c.ncam, getattr(c, 'cam_bodyid', None), getattr(c, 'cam_pos', None)),
                               ('light', c.nlight, c.light_bodyid, c.light_pos)):
     if pre + '_xpos' in need and n:
-      R = _quat_to_mat_rows(xquat[bodyid]).reshape(n, 3, 3)
+      R = host_data.quat_to_mat_rows(xquat[bodyid]).reshape(n, 3, 3)
       np.copyto(A[pre + '_xpos'], xpos[bodyid] + np.einsum('nij,nj->ni', R, pos))
   if 'cam_xmat' in need and c.ncam:
-    np.copyto(A['cam_xmat'], _quat_to_mat_rows(_quat_mul_rows(xquat[c.cam_bodyid], np.asarray(c.cam_quat, dtype=np.float64))))
+    np.copyto(A['cam_xmat'], host_data.quat_to_mat_rows(host_data.quat_mul_rows(xquat[c.cam_bodyid], np.asarray(c.cam_quat, dtype=np.float64))))
   if 'light_xdir' in need and c.nlight:
-    R = _quat_to_mat_rows(xquat[c.light_bodyid]).reshape(c.nlight, 3, 3)
+    R = host_data.quat_to_mat_rows(xquat[c.light_bodyid]).reshape(c.nlight, 3, 3)
     np.copyto(A['light_xdir'], np.einsum('nij,nj->ni', R, c.light_dir))
   if need & {'ten_length', 'ten_velocity', 'wrap_xpos'} and c.ntendon:
-    _tendons(d, dev)
+    sites = [dev('site_xpos', c.nsite, 3), dev('cvel', nb, 6), dev('subtree_com', nb, 3)] if host_data.spatial_tendons(c) else []
+    for n, val in zip(('ten_length', 'ten_velocity', 'wrap_xpos'), host_data.tendons(c, state('qpos'), state('qvel'), *sites)):
+      put(n, val)
   if 'act_dot' in need and c.na:
-    _act_dot(d)
+    put('act_dot', host_data.act_dot(c, x['actuator_actadr'], state('ctrl'), state('act')))
   if 'qfrc_passive' in need and c.nv:
-    _passive(d, dev)
+    put('qfrc_passive', host_data.passive(c, state('qpos'), state('qvel')))
   if need & {'subtree_linvel', 'subtree_angmom'}:
-    _subtree_vel(d, dev, xpos, ximat)
+    vel = host_data.subtree_vel(c, dev('cvel', nb, 6), dev('subtree_com', nb, 3), dev('xipos', nb, 3), ximat)
+    put('subtree_linvel', vel[0])
+    put('subtree_angmom', vel[1])
   if heavy and c.nv:
     xmat, xipos = dev('xmat', nb, 9), dev('xipos', nb, 3)
-    M = mass_matrix(c, xpos, xmat, xipos, ximat, anchor, axis)
+    M = host_data.mass_matrix(c, xpos, xmat, xipos, ximat, anchor, axis)
     if 'M' in A:
       rows = np.repeat(np.arange(c.nv), x['M_rownnz'])
       np.copyto(A['M'], M[rows, x['M_colind']])
@@ -1554,125 +1383,6 @@ def _derive(d, names):
         e[0], e[1] = pot, 0.5 * qv @ M @ qv
   elif 'energy' in need and 'energy' in A:
     A['energy'][:] = 0
-
-
-def _tendons(d, dev):
-  c, A = d._model._c, d._arrays
-  nt = c.ntendon
-  length, velocity = np.zeros(nt), np.zeros(nt)
-  wx = np.zeros((c.nwrap, 6))
-  qpos, qvel = d._shadow['qpos'].ravel(), d._shadow['qvel'].ravel()
-  spatial = [t for t in range(nt) if c.tendon_num[t] and c.wrap_type[c.tendon_adr[t]] != C['DMC_WRAP_JOINT']]
-  if spatial:
-    sx, cvel, com = dev('site_xpos', c.nsite, 3), dev('cvel', c.nbody, 6), dev('subtree_com', c.nbody, 3)
-  for t in range(nt):
-    w0, wn = int(c.tendon_adr[t]), int(c.tendon_num[t])
-    if t not in spatial:
-      for w in range(w0, w0 + wn):
-        j = int(c.wrap_objid[w])
-        length[t] += c.wrap_prm[w] * qpos[c.jnt_qposadr[j]]
-        velocity[t] += c.wrap_prm[w] * qvel[c.jnt_dofadr[j]]
-      continue
-
-    def point(w):
-      sid = int(c.wrap_objid[w])
-      bd = int(c.site_bodyid[sid])
-      p = sx[sid]
-      return p, cvel[bd, 3:] + np.cross(cvel[bd, :3], p - com[c.body_rootid[bd]])
-    for w in range(w0, w0 + wn - 1):
-      (p0, v0), (p1, v1) = point(w), point(w + 1)
-      wx[w, :3], wx[w, 3:] = p0, p1
-      dif = p1 - p0
-      n = np.linalg.norm(dif)
-      length[t] += n
-      if n > mjMINVAL:
-        velocity[t] += (dif / n) @ (v1 - v0)
-  for name, val in (('ten_length', length), ('ten_velocity', velocity), ('wrap_xpos', wx)):
-    if name in A:
-      np.copyto(A[name], val)
-
-
-def _passive(d, dev):
-  """mjData.qfrc_passive (mj_passive): joint springs and dampers, fixed-tendon springs and dampers.  Fluid forces and
-  ball / free joint springs are computed on the device only: a model that has them is refused here rather than served a
-  partial sum."""
-  c, A = d._model._c, d._arrays
-  if float(c.opt.density) or float(c.opt.viscosity):
-    raise NotImplementedError('mjData.qfrc_passive of a model with fluid forces is not derived on the host')
-  qpos, qvel = d._shadow['qpos'].ravel(), d._shadow['qvel'].ravel()
-  flags = int(c.opt.disableflags)
-  out = np.zeros(c.nv)
-  if not flags & C['DMC_DSBL_DAMPER']:
-    out -= np.asarray(c.dof_damping, dtype=np.float64) * qvel
-  if not flags & C['DMC_DSBL_SPRING']:
-    for j in range(c.njnt):
-      k = float(c.jnt_stiffness[j])
-      if not k:
-        continue
-      if c.jnt_type[j] not in (2, 3):
-        raise NotImplementedError('mjData.qfrc_passive with a spring on a ball / free joint is not derived on the host')
-      out[c.jnt_dofadr[j]] -= k * (qpos[c.jnt_qposadr[j]] - c.qpos_spring[c.jnt_qposadr[j]])
-  for t in range(c.ntendon):
-    ks, kd = float(c.tendon_stiffness[t]), float(c.tendon_damping[t])
-    if not (ks or kd):
-      continue
-    w0, wn = int(c.tendon_adr[t]), int(c.tendon_num[t])
-    js = [int(c.wrap_objid[w]) for w in range(w0, w0 + wn)]
-    coef = np.asarray(c.wrap_prm[w0:w0 + wn], dtype=np.float64)
-    length = float(coef @ qpos[np.asarray(c.jnt_qposadr)[js]])
-    vel = float(coef @ qvel[np.asarray(c.jnt_dofadr)[js]])
-    f = 0.0
-    if ks and not flags & C['DMC_DSBL_SPRING']:
-      f -= ks * (length - float(c.tendon_lengthspring[t]))
-    if kd and not flags & C['DMC_DSBL_DAMPER']:
-      f -= kd * vel
-    out[np.asarray(c.jnt_dofadr)[js]] += coef * f
-  np.copyto(A['qfrc_passive'], out)
-
-
-def _act_dot(d):
-  """mjData.act_dot (mj_fwdActuation): integrator `ctrl`, filter `(ctrl - act) / tau`; filterexact has the same rate."""
-  c, A = d._model._c, d._arrays
-  ctrl, act = d._shadow['ctrl'].ravel(), d._shadow['act'].ravel()
-  adr = _extras(c)['actuator_actadr']
-  out = np.zeros(c.na)
-  for i in range(c.nu):
-    if adr[i] < 0:
-      continue
-    u = ctrl[i]
-    if c.actuator_ctrllimited[i] and not int(c.opt.disableflags) & C['DMC_DSBL_CLAMPCTRL']:
-      u = min(max(u, c.actuator_ctrlrange[i, 0]), c.actuator_ctrlrange[i, 1])
-    t = int(c.actuator_dyntype[i])
-    if t == C['DMC_DYN_INTEGRATOR']:
-      out[adr[i]] = u
-    else:
-      out[adr[i]] = (u - act[adr[i]]) / max(mjMINVAL, c.actuator_dynprm[i, 0])
-  if int(c.opt.disableflags) & C['DMC_DSBL_ACTUATION']:
-    out[:] = 0
-  np.copyto(A['act_dot'], out)
-
-
-def _subtree_vel(d, dev, xpos, ximat):
-  """mj_subtreeVel: linear velocity of every subtree's centre of mass and its angular momentum about it, from the
-  device's com-based body velocities."""
-  del xpos
-  c, A = d._model._c, d._arrays
-  nb = c.nbody
-  cvel, com, xipos = dev('cvel', nb, 6), dev('subtree_com', nb, 3), dev('xipos', nb, 3)
-  mass = np.asarray(c.body_mass, dtype=np.float64)
-  sub = _extras(c)['subtree'].astype(np.float64)                  # (root, body)
-  ang = cvel[:, :3]
-  lin = cvel[:, 3:] + _cross(ang, xipos - com[np.asarray(c.body_rootid)])      # velocity of each body's own COM
-  msub = np.maximum(sub @ mass, mjMINVAL)
-  vsub = (sub @ (mass[:, None] * lin)) / msub[:, None]
-  if 'subtree_linvel' in A:
-    np.copyto(A['subtree_linvel'], vsub)
-  if 'subtree_angmom' in A:
-    R = ximat.reshape(nb, 3, 3)
-    spin = np.einsum('bij,bj,bkj,bk->bi', R, np.asarray(c.body_inertia, dtype=np.float64), R, ang)
-    # sum_b [I w + m (x - X) x (v - V)] = sum_b [I w + m x x v] - M X x V   (X, V: the subtree's centre of mass and its velocity)
-    own = spin + mass[:, None] * _cross(xipos, lin)
-    np.copyto(A['subtree_angmom'], sub @ own - msub[:, None] * _cross(com, vsub))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1776,13 +1486,7 @@ def _state_parts(m, sig):
   sig = int(sig)
   if sig < 0 or sig >= (1 << int(mjtState.mjNSTATE)):
     raise FatalError('mj_stateSize: invalid state signature %d' % sig)
-  c = m._c
-  nm = int(getattr(c, 'nmocap', 0))
-  sizes = {'TIME': 1, 'QPOS': c.nq, 'QVEL': c.nv, 'ACT': c.na, 'WARMSTART': c.nv, 'CTRL': c.nu, 'QFRC_APPLIED': c.nv,
-           'XFRC_APPLIED': 6 * c.nbody, 'EQ_ACTIVE': c.neq, 'MOCAP_POS': 3 * nm, 'MOCAP_QUAT': 4 * nm, 'USERDATA': 0, 'PLUGIN': 0}
-  field = {'QPOS': 'qpos', 'QVEL': 'qvel', 'ACT': 'act', 'WARMSTART': 'qacc_warmstart', 'CTRL': 'ctrl', 'QFRC_APPLIED': 'qfrc_applied',
-           'XFRC_APPLIED': 'xfrc_applied', 'EQ_ACTIVE': 'eq_active', 'MOCAP_POS': 'mocap_pos', 'MOCAP_QUAT': 'mocap_quat'}
-  return [(n, field.get(n), int(sizes[n])) for i, n in enumerate(_STATE_NAMES) if sig & (1 << i)]
+  return host_data.state_parts(m._c, sig)
 
 
 def mj_stateSize(m, sig):
@@ -1876,26 +1580,9 @@ def mj_contactForce(m, d, id_, result):
 def mj_objectVelocity(m, d, objtype, objid, res, flg_local):
   """core.py:522: 6D velocity (angular, linear) of a body / xbody / geom / site in the world or the object's own frame."""
   _check(m, d)
-  c = m._c
-  kinds = {1: ('body', 'xipos', None), 2: ('body', 'xpos', 'xmat'), 5: ('geom', 'geom_xpos', 'geom_xmat'), 6: ('site', 'site_xpos', 'site_xmat')}
-  if int(objtype) not in kinds:
+  if int(objtype) not in host_data.OBJECT_KINDS:
     raise FatalError('mj_objectVelocity: invalid object type %d' % int(objtype))
-  kind, posf, matf = kinds[int(objtype)]
-  get = lambda n, *shape: d._array(n).reshape(shape)
-  objid = int(objid)
-  body = objid if kind == 'body' else int(c.geom_bodyid[objid]) if kind == 'geom' else int(c.site_bodyid[objid])
-  n = {'body': c.nbody, 'geom': c.ngeom, 'site': c.nsite}[kind]
-  pos = get(posf, n, 3)[objid]
-  if matf is None:
-    mat = mjcf_compiler.quat_to_mat(mjcf_compiler.quat_mul(get('xquat', c.nbody, 4)[objid], c.body_iquat[objid]))
-  else:
-    mat = get(matf, n, 3, 3)[objid]
-  cvel = get('cvel', c.nbody, 6)[body]
-  com = get('subtree_com', c.nbody, 3)[int(c.body_rootid[body])]
-  ang = cvel[:3]
-  lin = cvel[3:] - np.cross(pos - com, ang)
-  if flg_local:
-    ang, lin = mat.T @ ang, mat.T @ lin
+  ang, lin = host_data.object_velocity(m._c, int(objtype), int(objid), lambda n, *shape: d._array(n).reshape(shape), flg_local)
   res = np.asarray(res).reshape(-1)
   res[:3], res[3:6] = ang, lin
 

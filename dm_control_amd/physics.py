@@ -22,8 +22,9 @@ import logging
 
 import numpy as np
 
+from dm_control_amd import host_data
 from dm_control_amd import mjcf_compiler
-from dm_control_amd.batch import BatchedPhysics
+from dm_control_amd.batch import BatchedPhysics      # (tests swap this name for the oracle stand-in)
 from dm_control_amd.envs import control
 from dm_control_amd.envs.dm_env_api import specs
 
@@ -31,14 +32,8 @@ mjMAXVAL = mjcf_compiler.C['DMC_MAXVAL']
 _WARNING_NAMES = ['mjWARN_INERTIA', 'mjWARN_CONTACTFULL', 'mjWARN_CNSTRFULL', 'mjWARN_VGEOMFULL',
                   'mjWARN_BADQPOS', 'mjWARN_BADQVEL', 'mjWARN_BADQACC', 'mjWARN_BADCTRL',
                   'dmcWARN_COLLISION']
-# model arrays tasks may rewrite through physics.model / physics.named.model between
-# episodes; changes are pushed to the device tables before the next launch
-_MUTABLE_MODEL_FIELDS = ('dof_damping', 'jnt_stiffness', 'jnt_range', 'jnt_margin', 'qpos_spring', 'site_pos',
-                         'site_quat', 'site_size', 'actuator_ctrlrange', 'actuator_forcerange', 'wrap_prm', 'body_pos',
-                         'body_quat',
-                         # geom frames / sizes as tasks rewrite them (suite/reacher.py:88-94, suite/fish.py:150-154:
-                         # the target geom); like MuJoCo, nothing derived at compile time (inertias, geom_rbound) follows
-                         'geom_pos', 'geom_quat', 'geom_size')
+# model arrays tasks may rewrite through physics.model / physics.named.model between episodes
+_MUTABLE_MODEL_FIELDS = host_data.MUTABLE_MODEL_FIELDS
 # rendering attributes: writable host arrays (suite/finger.py:139-140 site_rgba, suite/fish.py:115 geom_rgba,
 # suite/swimmer.py light_pos, suite/base.py:104-112 mat_rgba); they never reach the device
 _HOST_ONLY_MODEL_FIELDS = ('geom_rgba', 'site_rgba', 'mat_rgba', 'light_pos', 'light_dir',
@@ -49,8 +44,7 @@ _HOST_ONLY_MODEL_FIELDS = ('geom_rgba', 'site_rgba', 'mat_rgba', 'light_pos', 'l
 _STRUCTURAL_MODEL_FIELDS = ('geom_contype', 'geom_conaffinity')
 _INVALID_PHYSICS_STATE = ('Physics state is invalid. Warning(s) raised: {warning_names}')
 
-_INPUT_FIELDS = ('qpos', 'qvel', 'act', 'ctrl', 'qacc_warmstart', 'qfrc_applied', 'xfrc_applied', 'time', 'mocap_pos',
-                 'mocap_quat')
+_INPUT_FIELDS = host_data.INPUT_FIELDS + ('time',)
 _INT_FIELDS = ('ncon', 'nefc', 'solver_iter', 'warning', 'contact_geom1', 'contact_geom2')
 # field -> (row object kind for named access, columns per row)
 _FIELD_AXES = {
@@ -65,8 +59,8 @@ _FIELD_AXES = {
     'xpos': ('body', 3), 'xquat': ('body', 4), 'xmat': ('body', 9), 'xipos': ('body', 3),
     'subtree_com': ('body', 3), 'geom_xpos': ('geom', 3), 'geom_xmat': ('geom', 9),
     'site_xpos': ('site', 3), 'site_xmat': ('site', 9),
-    'xanchor': ('joint', 3), 'xaxis': ('joint', 3),      # derived on the host (_Data._joint_frames)
-    'ten_length': ('tendon', None), 'ten_velocity': ('tendon', None),      # derived on the host (_Data._tendons)
+    'xanchor': ('joint', 3), 'xaxis': ('joint', 3),      # derived on the host (host_data.joint_frames)
+    'ten_length': ('tendon', None), 'ten_velocity': ('tendon', None),      # derived on the host (host_data.tendons)
     'cvel': ('body', 6),      # com-based body velocities (rotational, translational): soccer/observables.py:278 reads them
 }
 _COLS = {3: ['x', 'y', 'z'], 4: ['qw', 'qx', 'qy', 'qz'], 6: ['fx', 'fy', 'fz', 'tx', 'ty', 'tz'],
@@ -112,95 +106,20 @@ class _Data:
     """MjData.ptr: an opaque handle (see Model.ptr)."""
     return self
 
-  def _joint_frames(self):
-    """mjData.xanchor / xaxis (joint anchors and axes in the world frame): mj_kinematics' joint loop replayed on the
-    host from qpos and the parents' frames -- each joint's anchor and axis are taken in the body frame accumulated
-    BEFORE that joint moves it, so bodies with several joints cannot be served from the final xpos / xmat."""
+  def _derived(self, name):
+    """xanchor / xaxis / ten_length / ten_velocity: derived on the host (host_data) from the device's state as of the
+    last launch -- like every derived array, edits not yet forwarded are not seen."""
     p, m = self._p, self._p.model
-    B = p.batch_size
-    qpos = np.asarray(p.batch.get('qpos'), dtype=np.float64).reshape(B, -1)
-    xpos = np.asarray(p.batch.get('xpos'), dtype=np.float64).reshape(B, -1, 3)
-    xquat = np.asarray(p.batch.get('xquat'), dtype=np.float64).reshape(B, -1, 4)
-    mpos = np.asarray(p.batch.get('mocap_pos'), dtype=np.float64).reshape(B, -1, 3) if getattr(m, 'nmocap', 0) else None
-    mquat = np.asarray(p.batch.get('mocap_quat'), dtype=np.float64).reshape(B, -1, 4) if getattr(m, 'nmocap', 0) else None
-    C = mjcf_compiler
-    anchor, axis = np.zeros((B, m.njnt, 3)), np.zeros((B, m.njnt, 3))
-    for e in range(B):
-      for b in range(1, m.nbody):
-        j0, jn = int(m.body_jntadr[b]), int(m.body_jntnum[b])
-        if jn == 0:
-          continue
-        if jn == 1 and m.jnt_type[j0] == 0:      # free joint
-          qa = int(m.jnt_qposadr[j0])
-          anchor[e, j0] = qpos[e, qa:qa + 3]
-          axis[e, j0] = m.jnt_axis[j0]
-          continue
-        pid = int(m.body_parentid[b])
-        bp, bq = m.body_pos[b], m.body_quat[b]
-        if getattr(m, 'nmocap', 0) and m.body_mocapid[b] >= 0:
-          bp, bq = mpos[e, m.body_mocapid[b]], mquat[e, m.body_mocapid[b]] / np.linalg.norm(mquat[e, m.body_mocapid[b]])
-        pos = xpos[e, pid] + C.quat_to_mat(xquat[e, pid]) @ bp if pid else np.array(bp, dtype=np.float64)
-        quat = C.quat_mul(xquat[e, pid], bq) if pid else np.array(bq, dtype=np.float64)
-        for j in range(j0, j0 + jn):
-          R = C.quat_to_mat(quat)
-          axis[e, j] = R @ m.jnt_axis[j]
-          anchor[e, j] = R @ m.jnt_pos[j] + pos
-          qa, t = int(m.jnt_qposadr[j]), int(m.jnt_type[j])
-          if t == 2:      # slide
-            pos = pos + axis[e, j] * (qpos[e, qa] - m.qpos0[qa])
-          else:           # ball / hinge: rotate about the anchor
-            if t == 1:
-              qloc = qpos[e, qa:qa + 4] / np.linalg.norm(qpos[e, qa:qa + 4])
-            else:
-              qloc = C.axisangle_to_quat(m.jnt_axis[j], qpos[e, qa] - m.qpos0[qa])
-            quat = C.quat_mul(quat, qloc)
-            pos = anchor[e, j] - C.quat_to_mat(quat) @ m.jnt_pos[j]
-    return anchor, axis
-
-  def _tendons(self):
-    """mjData.ten_length / ten_velocity (mj_tendon, mj_fwdVelocity: `ten_velocity = ten_J qvel`) from the device's state
-    as of the last launch -- the kernel re-derives the few tendon lengths where it needs them and stores none.  Fixed
-    tendons: the coefficient-weighted sum of joint coordinates / velocities; site-to-site spatial tendons: the segment
-    lengths, and their rates from the sites' velocities (com-based `cvel` of the body, moved to the site)."""
-    p, m = self._p, self._p.model
-    B, nt = p.batch_size, m.ntendon
-    length, velocity = np.zeros((B, nt)), np.zeros((B, nt))
-    get = lambda n, *shape: np.asarray(p.batch.get(n), dtype=np.float64).reshape((B,) + shape)
-    qpos, qvel = get('qpos', m.nq), get('qvel', m.nv)
-    spatial = [t for t in range(nt) if m.tendon_num[t] and m.wrap_type[m.tendon_adr[t]] != mjcf_compiler.C['DMC_WRAP_JOINT']]
-    if spatial:
-      sx, cvel, com = get('site_xpos', m.nsite, 3), get('cvel', m.nbody, 6), get('subtree_com', m.nbody, 3)
-    for t in range(nt):
-      w0, wn = int(m.tendon_adr[t]), int(m.tendon_num[t])
-      if t not in spatial:
-        for w in range(w0, w0 + wn):
-          j = int(m.wrap_objid[w])
-          length[:, t] += m.wrap_prm[w] * qpos[:, m.jnt_qposadr[j]]
-          velocity[:, t] += m.wrap_prm[w] * qvel[:, m.jnt_dofadr[j]]
-        continue
-      def point(w):
-        sid = int(m.wrap_objid[w])
-        b = int(m.site_bodyid[sid])
-        pos = sx[:, sid]
-        return pos, cvel[:, b, 3:] + np.cross(cvel[:, b, :3], pos - com[:, m.body_rootid[b]])
-      for w in range(w0, w0 + wn - 1):
-        (p0, v0), (p1, v1) = point(w), point(w + 1)
-        dif = p1 - p0
-        n = np.linalg.norm(dif, axis=-1)
-        length[:, t] += n
-        ok = n > mjcf_compiler.C['DMC_MINVAL']
-        velocity[ok, t] += np.einsum('ek,ek->e', dif[ok] / n[ok, None], (v1 - v0)[ok])
-    return length, velocity
+    get = lambda n, *shape: np.asarray(p.batch.get(n), dtype=np.float64).reshape((p.batch_size,) + shape)
+    if name in ('xanchor', 'xaxis'):
+      return host_data.joint_frames(m, get('qpos', m.nq), get('xpos', m.nbody, 3), get('xquat', m.nbody, 4))[name == 'xaxis']
+    sites = [get('site_xpos', m.nsite, 3), get('cvel', m.nbody, 6), get('subtree_com', m.nbody, 3)] if host_data.spatial_tendons(m) else []
+    return host_data.tendons(m, get('qpos', m.nq), get('qvel', m.nv), *sites)[name == 'ten_velocity']
 
   def _fetch(self, name):
     p = self._p
-    if name in ('ten_length', 'ten_velocity'):
-      a = self._tendons()[name == 'ten_velocity']
-      return a[0] if p.batch_size == 1 else a
-    if name in ('xanchor', 'xaxis'):
-      # (the device's state: like every derived array, as of the last launch -- edits not yet forwarded are not seen)
-      anchor, axis = self._joint_frames()
-      a = anchor if name == 'xanchor' else axis
+    if name in ('xanchor', 'xaxis', 'ten_length', 'ten_velocity'):
+      a = self._derived(name)
       return a[0] if p.batch_size == 1 else a
     a = self._prefetched.pop(name, None)
     if a is None:
@@ -307,13 +226,8 @@ class _Data:
         dev = self._shadow.get(name)
         if dev is not None and name not in self._written and dev.shape == a.shape and np.array_equal(a, dev, equal_nan=True):
           continue      # only read since the last launch: the device already holds these values
-      if name == 'xfrc_applied':
-        # A READ marks an input as touched too (the caller may have written into the array it was handed).  Uploading
-        # xfrc_applied switches the kernel's external-force path on for good (6 nbody reals per environment per step):
-        # all-zero forces are only sent once a non-zero one has been, i.e. when there is something to clear.
-        if not a.any() and not self._p.__dict__.get('_xfrc_sent', False):
-          continue
-        self._p._xfrc_sent = True
+      if name == 'xfrc_applied' and not host_data.send_xfrc(vars(p), a):
+        continue      # (a READ marks an input as touched too: the caller may have written into the array it was handed)
       send(name, a.reshape(p.batch_size, -1))
     self._touched.clear()
     self._written.clear()
@@ -363,11 +277,7 @@ class _Data:
     n = int(self._get('ncon'))
     out = np.zeros(n, dtype=[('geom1', np.int32), ('geom2', np.int32), ('dist', np.float64),
                              ('pos', np.float64, 3), ('frame', np.float64, 9)])
-    out['geom1'] = self._get('contact_geom1')[:n]
-    out['geom2'] = self._get('contact_geom2')[:n]
-    out['dist'] = self._get('contact_dist')[:n]
-    out['pos'] = self._get('contact_pos').reshape(-1, 3)[:n]
-    out['frame'] = self._get('contact_frame').reshape(-1, 9)[:n]
+    host_data.fill_contacts(out, n, self._get)
     # a record array: `contact.geom1` on the whole array AND on each element, as with mjData.contact
     # (locomotion/tasks/go_to_target.py:189-199 iterates it and reads `contact.geom1 / contact.geom2`)
     return out.view(np.recarray)
@@ -395,33 +305,13 @@ class _Data:
     mj_objectVelocity (wrapper/core.py:500-525) evaluated on the host from cvel / subtree_com."""
     p = self._p
     m = p.model
-    kinds = {'body': ('body', 'xipos', None), 'xbody': ('body', 'xpos', 'xmat'), 'geom': ('geom', 'geom_xpos', 'geom_xmat'),
-             'site': ('site', 'site_xpos', 'site_xmat'),
-             mjcf_compiler.C['DMC_OBJ_BODY']: ('body', 'xipos', None), mjcf_compiler.C['DMC_OBJ_XBODY']: ('body', 'xpos', 'xmat'),
-             mjcf_compiler.C['DMC_OBJ_GEOM']: ('geom', 'geom_xpos', 'geom_xmat'),
-             mjcf_compiler.C['DMC_OBJ_SITE']: ('site', 'site_xpos', 'site_xmat')}
-    if object_type not in kinds:
+    if object_type not in host_data.OBJECT_KINDS:
       raise ValueError('{!r} is not a valid object type for object_velocity'.format(object_type))
-    kind, posf, matf = kinds[object_type]
     if not isinstance(object_id, (int, np.integer)):
-      object_id = m.name2id(object_id, kind)
+      object_id = m.name2id(object_id, host_data.OBJECT_KINDS[object_type][0])
     B = p.batch_size
-    body = {'body': object_id, 'geom': m.geom_bodyid[object_id] if kind == 'geom' else None,
-            'site': m.site_bodyid[object_id] if kind == 'site' else None}[kind]
-    pos = p.batch.get(posf).reshape(B, -1, 3)[:, object_id]
-    if matf is None:     # inertial frame of a body: orientation xquat * body_iquat
-      q = p.batch.get('xquat').reshape(B, -1, 4)[:, object_id]
-      mat = np.stack([mjcf_compiler.quat_to_mat(mjcf_compiler.quat_mul(q[e], m.body_iquat[object_id])) for e in range(B)])
-    else:
-      mat = p.batch.get(matf).reshape(B, -1, 3, 3)[:, object_id]
-    cvel = p.batch.get('cvel').reshape(B, -1, 6)[:, body]
-    root = m.body_rootid[body]
-    com = p.batch.get('subtree_com').reshape(B, -1, 3)[:, root]
-    ang = cvel[:, :3]
-    lin = cvel[:, 3:] - np.cross(pos - com, ang)
-    if local_frame:
-      ang = np.einsum('bij,bi->bj', mat, ang)
-      lin = np.einsum('bij,bi->bj', mat, lin)
+    get = lambda n, *shape: np.asarray(p.batch.get(n), dtype=np.float64).reshape((B,) + shape)
+    ang, lin = host_data.object_velocity(m, object_type, object_id, get, local_frame)
     out = np.stack([lin, ang], axis=1)
     return out[0] if B == 1 else out
 
@@ -511,8 +401,9 @@ class _Named:
 
 def _make_axes(model):
   m = model
-  jq = _Axis(m.names['joint'], m.jnt_qposadr, [{0: 7, 1: 4, 2: 1, 3: 1}[t] for t in m.jnt_type])
-  jv = _Axis(m.names['joint'], m.jnt_dofadr, [{0: 6, 1: 3, 2: 1, 3: 1}[t] for t in m.jnt_type])
+  qadr, qnum, vadr, vnum = host_data.joint_spans(m)
+  jq = _Axis(m.names['joint'], qadr, qnum)
+  jv = _Axis(m.names['joint'], vadr, vnum)
   return {
       'joint_q': jq, 'joint_v': jv,
       'actuator': _Axis(m.names['actuator']),
@@ -623,21 +514,11 @@ class Physics(control.Physics):
         raise
       logging.getLogger(__name__).warning('at the model\'s qpos0: %s', e)
 
-  # contact capacities tried, in order, when the caller names none: MuJoCo sizes its contact buffer from an arena (any
-  # number of contacts a model can produce fits), a drop-in user never sets `nconmax` -- so the facade asks for a generous
-  # cap first and settles for less only where the model's scratch would not fit in LDS.  (The throughput path,
-  # BatchedPhysics / suite.load, keeps its tuned per-model caps: suite/common.py DEFAULT_CAPS.)
-  _AUTO_NCONMAX = (64, 48, 32, 0)
-
   def _create_batch(self, model, device_id, precision, batch_kwargs):
+    kw = dict(batch_kwargs, device_id=device_id, precision=precision)
     if 'nconmax' in batch_kwargs or self.batch_size > 64:
-      return BatchedPhysics(model, self.batch_size, device_id=device_id, precision=precision, **batch_kwargs)
-    for cap in self._AUTO_NCONMAX:
-      try:
-        return BatchedPhysics(model, self.batch_size, device_id=device_id, precision=precision, nconmax=cap, **batch_kwargs)
-      except Exception as e:      # pylint: disable=broad-except
-        if cap == 0 or 'does not fit' not in str(e):
-          raise
+      return BatchedPhysics(model, self.batch_size, **kw)
+    return host_data.create_batch(BatchedPhysics, model, self.batch_size, **kw)      # (the caller names no contact capacity)
 
   def _reload_from_data(self, data):
     """The hook engine.Physics calls whenever it (re)binds an mjData (engine.py:392-430): subclasses override it to
@@ -676,7 +557,7 @@ class Physics(control.Physics):
       batch = self._create_batch(model, self._batch_kwargs.get('device_id', 0), old.precision, kw)
     for name in _INPUT_FIELDS:
       a = np.asarray(old.get(name), dtype=np.float64).reshape(self.batch_size, -1)
-      if name == 'xfrc_applied' and not a.any():
+      if name == 'xfrc_applied' and not host_data.send_xfrc({}, a):
         continue
       batch.set(name, a)
     self.batch = batch      # (created from the model's current arrays and options: nothing else to re-send)
@@ -813,28 +694,11 @@ class Physics(control.Physics):
     self.batch.enable_profiling(True)
 
   # -- state -------------------------------------------------------------------------------
-  # mjtState bits (mujoco 3.x), in the order mj_getState concatenates them
-  _STATE_BITS = (('time', 1 << 0), ('qpos', 1 << 1), ('qvel', 1 << 2), ('act', 1 << 3), ('qacc_warmstart', 1 << 4),
-                 ('ctrl', 1 << 5), ('qfrc_applied', 1 << 6), ('xfrc_applied', 1 << 7), ('eq_active', 1 << 8),
-                 ('mocap_pos', 1 << 9), ('mocap_quat', 1 << 10), ('userdata', 1 << 11), ('plugin_state', 1 << 12))
-
   def _state_components(self, sig):
-    if not isinstance(sig, (int, np.integer)) or sig <= 0 or sig >= (1 << 13):
+    """[(mjData field, size)] of the mjtState components `sig` selects, in the order mj_getState concatenates them."""
+    if not isinstance(sig, (int, np.integer)) or sig <= 0 or sig >= (1 << host_data.NSTATE):
       raise ValueError('invalid state signature: {!r}'.format(sig))
-    out = []
-    for name, bit in self._STATE_BITS:
-      if not sig & bit:
-        continue
-      if name == 'eq_active':
-        n = len(getattr(self.model, 'eq_active0', ()))
-        out.append((name, n))
-      elif name in ('mocap_pos', 'mocap_quat'):
-        out.append((name, (3 if name == 'mocap_pos' else 4) * int(getattr(self.model, 'nmocap', 0))))
-      elif name in ('userdata', 'plugin_state'):
-        out.append((name, 0))            # no user data / plugins in a compiled Model
-      else:
-        out.append((name, int(np.asarray(self.data._get(name)).reshape(self.batch_size, -1).shape[1])))
-    return out
+    return [(field or name.lower(), n) for name, field, n in host_data.state_parts(self.model, sig)]
 
   def get_state(self, sig=None):
     """sig None: concatenated [qpos, qvel, act] (engine.py:235-249); otherwise what `mj_getState(sig)` returns
@@ -892,10 +756,8 @@ class Physics(control.Physics):
         setattr(other, k, _copy.deepcopy(v))
     for name in _INPUT_FIELDS:
       a = np.asarray(self.data._get(name), dtype=np.float64).reshape(self.batch_size, -1)
-      if name == 'xfrc_applied':
-        other._xfrc_sent = bool(a.any())
-        if not a.any():
-          continue      # (a fresh batch holds zeros; sending them would switch its external-force path on for good)
+      if name == 'xfrc_applied' and not host_data.send_xfrc(vars(other), a):
+        continue      # (a fresh batch holds zeros; sending them would switch its external-force path on for good)
       other.batch.set(name, a)
     other.legacy_step = self.legacy_step
     other.data._invalidate()
@@ -926,10 +788,8 @@ class Physics(control.Physics):
     Physics.__init__(self, st['cls_model'], batch_size=st['batch_size'], precision=st['precision'],
                      **st.get('batch_kwargs', {}))
     for n, v in st['fields'].items():
-      if n == 'xfrc_applied':
-        self._xfrc_sent = bool(np.asarray(v).any())
-        if not self._xfrc_sent:
-          continue
+      if n == 'xfrc_applied' and not host_data.send_xfrc(vars(self), v):
+        continue
       self.batch.set(n, v)
     self.legacy_step = st['legacy_step']
     for k, v in st.get('attrs', {}).items():

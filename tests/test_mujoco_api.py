@@ -19,6 +19,7 @@ import pytest
 
 from dm_control_amd import mjcf_compiler
 from dm_control_amd import mujoco_api as mj
+from joint_frames_walk import joint_frames_walk
 
 _ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'dm_control_amd', 'suite', 'assets')
 
@@ -113,13 +114,8 @@ def _check_derivations(backend_oracle_of):
     L = np.tril(L, -1) + np.eye(nv)
     np.testing.assert_allclose(L.T @ np.diag(D) @ L, dense, rtol=0, atol=1e-10 * np.abs(dense).max())
     np.testing.assert_allclose(d.qLDiagInv, 1 / D, rtol=1e-13)
-    # xanchor / xaxis against mj_kinematics' own forward walk (the facade's restatement: an independent code path)
-    from dm_control_amd import physics as facade
-    fake = type('P', (), {})()
-    fake.batch_size, fake.model = 1, c
-    fake.batch = type('B', (), {'get': staticmethod(lambda n: np.asarray(getattr(d, n), dtype=np.float64).reshape(1, -1))})()
-    holder = type('D', (), {'_p': fake})()
-    anchor, axis = facade._Data._joint_frames(holder)
+    # xanchor / xaxis against mj_kinematics' own forward walk (tests/joint_frames_walk.py: an independent code path)
+    anchor, axis = joint_frames_walk(c, d.qpos[None], d.xpos[None], d.xquat[None], d.mocap_pos[None], d.mocap_quat[None])
     np.testing.assert_allclose(d.xanchor, anchor[0], rtol=0, atol=1e-12)
     np.testing.assert_allclose(d.xaxis, axis[0], rtol=0, atol=1e-12)
     # ximat = xquat * body_iquat
