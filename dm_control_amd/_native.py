@@ -24,6 +24,9 @@ EXPORTS = [
     'dmc_camera_render',
 ]
 
+# include/dmc_ik.h (batched inverse kinematics: csrc/ik_kernels.hip)
+IK_EXPORTS = ['dmc_ik_last_error', 'dmc_ik_create', 'dmc_ik_solve', 'dmc_ik_info', 'dmc_ik_destroy']
+
 _lib = None
 
 
@@ -111,6 +114,13 @@ def lib():
       L.dmc_camera_set_materials.argtypes = [vp, vp, vp, ci]
     L.dmc_camera_set_tuning.argtypes = [vp, ci, ci]
     L.dmc_camera_render.argtypes = [vp, ci, vp, vp, vp, vp]
+  if hasattr(L, 'dmc_ik_create'):      # (absent from the older libraries A/B runs load as variants)
+    L.dmc_ik_last_error.restype = cs
+    L.dmc_ik_create.argtypes = [vp, vp, vp, ctypes.POINTER(vp)]
+    L.dmc_ik_solve.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.dmc_ik_info.argtypes = [vp, vp]
+    L.dmc_ik_destroy.argtypes = [vp]
+    L.dmc_ik_destroy.restype = None
   _lib = L
   return L
 

@@ -319,16 +319,82 @@ def object_velocity(c, kind, objid, get, local):
 # ---------------------------------------------------------------------------------------------------------------------
 # derivations only MjData serves (one environment)
 # ---------------------------------------------------------------------------------------------------------------------
+def dof_axes(c, xpos, xmat, xanchor, xaxis):
+  """Per dof: its world axis (nv, 3), the point its rotation passes through (nv, 3) and whether it rotates (nv,) -- a
+  hinge's or slide's joint axis, the columns of the body's orientation for a ball joint and the rotations of a free
+  joint, the world axes for a free joint's translations (mj_comPos's cdof, in world terms)."""
+  p = _plan(c, _dof_plan)
+  R = np.asarray(xmat, dtype=np.float64).reshape(c.nbody, 3, 3)
+  axis = np.where((p['kind'] == 2)[:, None], xaxis[p['jnt']], R[p['body'], :, p['col']])
+  axis = np.where((p['kind'] == 0)[:, None], np.eye(3)[p['col']], axis)
+  anchor = np.where(p['free_rot'][:, None], xpos[p['body']], xanchor[p['jnt']])
+  return axis, anchor, p['rot']
+
+
+def point_jacobian(c, body, point, xpos, xmat, xanchor, xaxis):
+  """mj_jac: (jacp (3, nv), jacr (3, nv)) of the world point `point` moving with body `body`."""
+  axis, anchor, rot = dof_axes(c, xpos, xmat, xanchor, xaxis)
+  mask = _plan(c, _body_dofmask)[int(body)]
+  r = np.asarray(point, dtype=np.float64)[None, :] - anchor
+  jp = np.where(rot[:, None], cross(axis, r), axis) * mask[:, None]
+  jr = np.where(rot[:, None], axis, 0.0) * mask[:, None]
+  return jp.T.copy(), jr.T.copy()
+
+
+def _quat_integrate(q, v, dt):
+  """mju_quatIntegrate: q (4,) turned by the local angular velocity v (3,) over dt."""
+  n = np.linalg.norm(v)
+  ax = v / n if n >= MINVAL else np.array([1.0, 0, 0])
+  ang = dt * n
+  qn = np.linalg.norm(q)
+  q = np.array([1.0, 0, 0, 0]) if qn < MINVAL else q / qn if abs(qn - 1) > MINVAL else q
+  return quat_mul_rows(q, np.concatenate([[np.cos(ang / 2)], ax * np.sin(ang / 2)]))
+
+
+def integrate_pos(c, qpos, qvel, dt):
+  """mj_integratePos: `qpos` (nq,) advanced in place by `qvel` (nv,) over dt; ball and free rotations compose on the
+  right, in local axes."""
+  for j in range(c.njnt):
+    t, a, d = int(c.jnt_type[j]), int(c.jnt_qposadr[j]), int(c.jnt_dofadr[j])
+    if t == 0:
+      qpos[a:a + 3] += dt * qvel[d:d + 3]
+      qpos[a + 3:a + 7] = _quat_integrate(qpos[a + 3:a + 7], qvel[d + 3:d + 6], dt)
+    elif t == 1:
+      qpos[a:a + 4] = _quat_integrate(qpos[a:a + 4], qvel[d:d + 3], dt)
+    else:
+      qpos[a] += dt * qvel[d]
+
+
+def _quat_sub(qa, qb):
+  """mju_subQuat: the local rotation vector that takes qb to qa."""
+  q = quat_mul_rows(qb * np.array([1.0, -1, -1, -1]), qa)
+  ax = q[1:4].copy()
+  s = np.linalg.norm(ax)
+  ax = ax / s if s >= MINVAL else np.array([1.0, 0, 0])
+  ang = 2 * np.arctan2(s, q[0])
+  if ang > np.pi:
+    ang -= 2 * np.pi
+  return ax * ang
+
+
+def differentiate_pos(c, qvel, dt, qpos1, qpos2):
+  """mj_differentiatePos: `qvel` (nv,) := (qpos2 - qpos1) / dt, the inverse of integrate_pos."""
+  for j in range(c.njnt):
+    t, a, d = int(c.jnt_type[j]), int(c.jnt_qposadr[j]), int(c.jnt_dofadr[j])
+    if t == 0:
+      qvel[d:d + 3] = (qpos2[a:a + 3] - qpos1[a:a + 3]) / dt
+      qvel[d + 3:d + 6] = _quat_sub(qpos2[a + 3:a + 7], qpos1[a + 3:a + 7]) / dt
+    elif t == 1:
+      qvel[d:d + 3] = _quat_sub(qpos2[a:a + 4], qpos1[a:a + 4]) / dt
+    else:
+      qvel[d] = (qpos2[a] - qpos1[a]) / dt
+
+
 def mass_matrix(c, xpos, xmat, xipos, ximat, xanchor, xaxis):
   """Dense joint-space inertia M(q) (what mj_crb leaves in mjData.M) from world-frame body Jacobians:
   M = sum_b m_b Jp_b' Jp_b + Jr_b' (R_b I_b R_b') Jr_b + diag(dof_armature)."""
   nv, nb = c.nv, c.nbody
-  p = _plan(c, _dof_plan)
-  R = np.asarray(xmat, dtype=np.float64).reshape(nb, 3, 3)
-  axis = np.where((p['kind'] == 2)[:, None], xaxis[p['jnt']], R[p['body'], :, p['col']])
-  axis = np.where((p['kind'] == 0)[:, None], np.eye(3)[p['col']], axis)
-  anchor = np.where(p['free_rot'][:, None], xpos[p['body']], xanchor[p['jnt']])
-  rot = p['rot']
+  axis, anchor, rot = dof_axes(c, xpos, xmat, xanchor, xaxis)
   mask = _plan(c, _body_dofmask)                             # (nb, nv)
   r = xipos[:, None, :] - anchor[None, :, :]                 # (nb, nv, 3)
   jp = np.where(rot[None, :, None], cross(np.broadcast_to(axis[None, :, :], r.shape), r), axis[None, :, :]) * mask[:, :, None]

@@ -1435,6 +1435,46 @@ def mj_kinematics(m, d):
 mj_comPos = mj_comVel = mj_tendon = mj_kinematics
 
 
+def mj_jac(m, d, jacp, jacr, point, body):
+  """The Jacobian of a world point moving with `body` (utils/inverse_kinematics.py:179-180 through mj_jacSite): `jacp` /
+  `jacr`, (3, nv) each or None, are written in place.  Like MuJoCo's it reads the kinematics as they stand: the caller
+  runs mj_fwdPosition (or mj_kinematics) first."""
+  _check(m, d)
+  c = m._c
+  if not d._outputs_valid:
+    d._ensure_forward()
+  get = lambda n, *shape: np.asarray(d._batch.get(n), dtype=np.float64).reshape(shape)
+  xpos, xquat = get('xpos', c.nbody, 3), get('xquat', c.nbody, 4)
+  anchor, axis = host_data.joint_frames(c, d._shadow['qpos'].ravel(), xpos, xquat)
+  jp, jr = host_data.point_jacobian(c, int(body), np.asarray(point, dtype=np.float64).ravel(), xpos,
+                                    host_data.quat_to_mat_rows(xquat), anchor, axis)
+  if jacp is not None:
+    np.asarray(jacp).reshape(3, c.nv)[...] = jp
+  if jacr is not None:
+    np.asarray(jacr).reshape(3, c.nv)[...] = jr
+
+
+def mj_jacBody(m, d, jacp, jacr, body):
+  mj_jac(m, d, jacp, jacr, np.asarray(d._batch.get('xpos'), dtype=np.float64).reshape(-1, 3)[int(body)], body)
+
+
+def mj_jacSite(m, d, jacp, jacr, site):
+  """utils/inverse_kinematics.py:179-180."""
+  mj_jac(m, d, jacp, jacr, np.asarray(d._batch.get('site_xpos'), dtype=np.float64).reshape(-1, 3)[int(site)],
+         int(m._c.site_bodyid[int(site)]))
+
+
+def mj_integratePos(m, qpos, qvel, dt):
+  """utils/inverse_kinematics.py:208: `qpos` advanced in place."""
+  q = np.asarray(qpos)
+  host_data.integrate_pos(m._c, q, np.asarray(qvel, dtype=np.float64), float(dt))
+
+
+def mj_differentiatePos(m, qvel, dt, qpos1, qpos2):
+  host_data.differentiate_pos(m._c, np.asarray(qvel), float(dt), np.asarray(qpos1, dtype=np.float64),
+                              np.asarray(qpos2, dtype=np.float64))
+
+
 def mj_subtreeVel(m, d):
   """legacy_base.py:148,186: the device serves subtree velocities to its sensors itself; the mjData arrays are derived on
   the host whenever they have been handed out."""
