@@ -27,6 +27,9 @@ EXPORTS = [
 # include/dmc_ik.h (batched inverse kinematics: csrc/ik_kernels.hip)
 IK_EXPORTS = ['dmc_ik_last_error', 'dmc_ik_create', 'dmc_ik_solve', 'dmc_ik_info', 'dmc_ik_destroy']
 
+# include/dmc_ray.h (batched ray casts: csrc/ray_kernels.hip)
+RAY_EXPORTS = ['dmc_rays_create', 'dmc_rays_cast', 'dmc_rays_add_scan', 'dmc_rays_scan', 'dmc_rays_info', 'dmc_rays_destroy']
+
 _lib = None
 
 
@@ -121,6 +124,14 @@ def lib():
     L.dmc_ik_info.argtypes = [vp, vp]
     L.dmc_ik_destroy.argtypes = [vp]
     L.dmc_ik_destroy.restype = None
+  if hasattr(L, 'dmc_rays_create'):      # (absent from the older libraries A/B runs load as variants)
+    L.dmc_rays_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    L.dmc_rays_cast.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp]
+    L.dmc_rays_add_scan.argtypes = [vp, ci, ci, vp, ci, ci, vp]
+    L.dmc_rays_scan.argtypes = [vp, vp, vp, vp, vp]
+    L.dmc_rays_info.argtypes = [vp, vp]
+    L.dmc_rays_destroy.argtypes = [vp]
+    L.dmc_rays_destroy.restype = None
   _lib = L
   return L
 

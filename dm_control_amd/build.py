@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU.  The library is git-ignored but travels to
 the GPU box with the working-tree snapshot.
 """
 import os
+import re
 import subprocess
 import sys
 
@@ -38,6 +39,9 @@ _UNITS = [
     # no contraction: the fp64 instantiation rounds like the host build the tests compare it with
     ('ik_kernels.hip', ['-ffp-contract=off'], ['ik_core.h', 'step_defs.h', 'step_math.h', '../../include/dmc_model_layout.h',
                                                '../../include/dmc_ik.h', '../../include/dmc_batch.h']),
+    # batched ray casts (fp32 and fp64: arbitrary rays, scans in a moving frame); the closed forms are the camera's
+    ('ray_kernels.hip', [], ['ray_core.h', 'camera_core.h', '../../include/dmc_model_layout.h']),
+    # (the ray entry points' headers, ray_core.h and dmc_ray.h, reach the staleness check through _own_includes)
     ('dmc_api.hip', [], list(STEP_SOURCES) + ['camera_core.h']),
 ]
 
@@ -47,6 +51,15 @@ def _stale(target, sources):
     return True
   t = os.path.getmtime(target)
   return any(os.path.getmtime(s) > t for s in sources)
+
+
+def _own_includes(src):
+  """The files a unit's own text includes with quotes, where they exist: a unit is stale against them whether or not its
+  _UNITS entry lists them."""
+  with open(src) as f:
+    names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+  paths = [os.path.normpath(os.path.join(os.path.dirname(src), n)) for n in names]
+  return [p for p in paths if os.path.exists(p)]
 
 
 # suite models that get model-specialised kernel instantiations: (asset, [lanes...], (nconmax, njmax[, njcon])); the caps
@@ -122,7 +135,7 @@ def build(force=False, verbose=False, profile=False, variant=None, extra_flags=(
     if profile:
       flags = flags + ['-DDMC_PROFILE=1']
     objs.append(o)
-    if force or _stale(o, [s] + udeps):
+    if force or _stale(o, [s] + udeps + _own_includes(s)):
       cmd = [HIPCC] + _COMMON + flags + ['-c', s, '-o', o]
       if verbose:
         print(' '.join(cmd), file=sys.stderr)

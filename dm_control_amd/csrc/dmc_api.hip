@@ -1587,3 +1587,163 @@ extern "C" int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, vo
   return b->precision == 64 ? camera_render_t<double>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream)
                             : camera_render_t<float>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream);
 }
+
+// ---- batched ray casts (ray_core.h, ray_kernels.hip; include/dmc_ray.h) ------------------------------------------
+#include "../../include/dmc_ray.h"
+#include "ray_core.h"
+struct dmc_rays {
+  dmc_batch* b;
+  int ngeom, nlist, nscan, ndir, scan_mask;
+  double cutoff;
+  int *d_type, *d_body, *d_list;
+  void* d_scans; void* d_dirs;      // RayScan<T>[nscan], T (nscan, ndir, 3) in the batch precision
+  std::vector<dmc::RayScan<double>> scans;
+  std::vector<double> dirs;
+};
+static void rays_free(void** p) { if (*p) (void)hipFree(*p); *p = nullptr; }
+extern "C" int dmc_rays_create(dmc_batch* b, const dmc_rays_options* opt, dmc_rays** out) {
+  if (!b || !opt || !out) return fail("null argument");
+  const HostModel& m = b->model->hm;
+  if (m.ngeom > 0 && (!opt->geom_group || opt->ngeom_group != m.ngeom)) return fail("rays: geom_group must hold one group per geom of the model");
+  if (opt->cutoff != opt->cutoff) return fail("rays: cutoff is NaN");
+  std::vector<int> type(std::max(1, m.ngeom)), body(std::max(1, m.ngeom)), list;
+  for (int g = 0; g < m.ngeom; g++) {
+    type[g] = m.geom_type[g];
+    body[g] = m.geom_bodyid[g];
+    if (body[g] < 0 || body[g] >= m.nbody) return fail("rays: geom body out of range");
+    const int grp = std::min(5, std::max(0, opt->geom_group[g]));
+    const bool solid = type[g] == DMC_GEOM_PLANE || type[g] == DMC_GEOM_SPHERE || type[g] == DMC_GEOM_CAPSULE ||
+                       type[g] == DMC_GEOM_ELLIPSOID || type[g] == DMC_GEOM_CYLINDER || type[g] == DMC_GEOM_BOX;
+    if (!solid || m.geom_invisible[g] || (opt->has_geomgroup && !opt->geomgroup[grp]) ||
+        (!opt->flg_static && m.body_weldid[body[g]] == 0)) continue;
+    list.push_back(g);
+  }
+  dmc_rays* r = new dmc_rays();
+  r->b = b; r->ngeom = m.ngeom; r->nlist = (int)list.size(); r->nscan = 0; r->ndir = 0; r->scan_mask = 0;
+  r->cutoff = (opt->cutoff > 0 && opt->cutoff < 1e30) ? opt->cutoff : (double)INFINITY;
+  r->d_type = nullptr; r->d_body = nullptr; r->d_list = nullptr; r->d_scans = nullptr; r->d_dirs = nullptr;
+  list.resize(std::max<size_t>(1, list.size()), 0);
+  hipError_t e = hipSetDevice(b->device);
+  const size_t ni = sizeof(int)*type.size();
+  if (e == hipSuccess) e = hipMalloc((void**)&r->d_type, ni);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->d_body, ni);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->d_list, sizeof(int)*list.size());
+  if (e == hipSuccess) e = hipMemcpy(r->d_type, type.data(), ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r->d_body, body.data(), ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r->d_list, list.data(), sizeof(int)*list.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { dmc_rays_destroy(r); return fail(std::string("rays create: ") + hipGetErrorString(e), -2); }
+  *out = r;
+  return 0;
+}
+extern "C" void dmc_rays_destroy(dmc_rays* r) {
+  if (!r) return;
+  rays_free((void**)&r->d_type); rays_free((void**)&r->d_body); rays_free((void**)&r->d_list);
+  rays_free(&r->d_scans); rays_free(&r->d_dirs);
+  delete r;
+}
+extern "C" int dmc_rays_info(const dmc_rays* r, int* info) {
+  if (!r || !info) return fail("null argument");
+  const int v[8] = {r->b->B, r->b->precision, r->nlist, r->nscan, r->ndir, kRayBlock, kRayTile, kRayPass};
+  for (int k = 0; k < 8; k++) info[k] = v[k];
+  return 0;
+}
+template <typename T>
+static int rays_upload_scans(dmc_rays* r) {
+  std::vector<RayScan<T>> s(r->scans.size());
+  for (size_t i = 0; i < s.size(); i++) {
+    const RayScan<double>& h = r->scans[i];
+    s[i].frame_type = h.frame_type; s[i].frame_id = h.frame_id; s[i].bodyexclude = h.bodyexclude; s[i].pad = 0; s[i].pad2 = 0;
+    for (int k = 0; k < 3; k++) s[i].offset[k] = (T)h.offset[k];
+  }
+  std::vector<T> d(r->dirs.begin(), r->dirs.end());
+  void *ds = nullptr, *dd = nullptr;
+  hipError_t e = hipMalloc(&ds, sizeof(s[0])*s.size());
+  if (e == hipSuccess) e = hipMalloc(&dd, sizeof(T)*d.size());
+  if (e == hipSuccess) e = hipMemcpy(ds, s.data(), sizeof(s[0])*s.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dd, d.data(), sizeof(T)*d.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { rays_free(&ds); rays_free(&dd); return fail(std::string("rays add_scan: ") + hipGetErrorString(e), -2); }
+  HIP_TRY(hipDeviceSynchronize());      // (a launch in flight may still read the tables this replaces)
+  rays_free(&r->d_scans); rays_free(&r->d_dirs);
+  r->d_scans = ds; r->d_dirs = dd;
+  return 0;
+}
+extern "C" int dmc_rays_add_scan(dmc_rays* r, int frame_type, int frame_id, const double* offset, int bodyexclude, int ndir,
+                                 const double* dirs_host) {
+  if (!r || !offset || !dirs_host) return fail("null argument");
+  const HostModel& m = r->b->model->hm;
+  if (frame_type < RAY_FRAME_WORLD || frame_type > RAY_FRAME_GEOM) return fail("rays scan: frame type must be 0 world, 1 body, 2 site or 3 geom");
+  const int nframe = frame_type == RAY_FRAME_BODY ? m.nbody : frame_type == RAY_FRAME_SITE ? m.nsite : frame_type == RAY_FRAME_GEOM ? m.ngeom : 1;
+  if (frame_type == RAY_FRAME_WORLD) frame_id = 0;
+  if (frame_id < 0 || frame_id >= nframe) return fail("rays scan: frame id out of range");
+  if (bodyexclude < -1 || bodyexclude >= m.nbody) return fail("rays scan: bodyexclude out of range");
+  if (ndir < 1) return fail("rays scan: no directions");
+  if (r->nscan && ndir != r->ndir) return fail("rays scan: every scan of one object has the same number of directions");
+  for (int k = 0; k < 3*ndir; k++) if (!(fabs(dirs_host[k]) < 1e30)) return fail("rays scan: a direction is not finite");
+  for (int k = 0; k < 3; k++) if (!(fabs(offset[k]) < 1e30)) return fail("rays scan: the offset is not finite");
+  RayScan<double> s;
+  s.frame_type = frame_type; s.frame_id = frame_id; s.bodyexclude = bodyexclude; s.pad = 0; s.pad2 = 0;
+  for (int k = 0; k < 3; k++) s.offset[k] = offset[k];
+  r->scans.push_back(s);
+  r->dirs.insert(r->dirs.end(), dirs_host, dirs_host + 3*(size_t)ndir);
+  HIP_TRY(hipSetDevice(r->b->device));
+  const int rc = r->b->precision == 64 ? rays_upload_scans<double>(r) : rays_upload_scans<float>(r);
+  if (rc) { r->scans.pop_back(); r->dirs.resize(r->dirs.size() - 3*(size_t)ndir); return rc; }
+  r->nscan = (int)r->scans.size(); r->ndir = ndir;
+  r->scan_mask |= frame_type == RAY_FRAME_BODY ? (OUT_XPOS | OUT_XMAT) : frame_type == RAY_FRAME_SITE ? OUT_SITE : 0;
+  return 0;
+}
+static int launch_rays(const RayArgs<float>& a, bool scan, void* s) { return scan ? launch_ray_scan_f32(a, s) : launch_ray_cast_f32(a, s); }
+static int launch_rays(const RayArgs<double>& a, bool scan, void* s) { return scan ? launch_ray_scan_f64(a, s) : launch_ray_cast_f64(a, s); }
+template <typename T>
+static int rays_launch_t(dmc_rays* r, bool scan, int nray, const void* pnt, const void* vec, int bex, const int32_t* bex_dev,
+                         int per_ray, void* dist, int32_t* geomid, void* normal, void* stream) {
+  dmc_batch* b = r->b;
+  RayArgs<T> a;
+  a.geom_xpos = (const T*)b->fields[F_geom_xpos].dev; a.geom_xmat = (const T*)b->fields[F_geom_xmat].dev;
+  a.xpos = (const T*)b->fields[F_xpos].dev; a.xmat = (const T*)b->fields[F_xmat].dev;
+  a.site_xpos = (const T*)b->fields[F_site_xpos].dev; a.site_xmat = (const T*)b->fields[F_site_xmat].dev;
+  a.geom_size = (const T*)b->d_mr + b->tb.L.mr_geom_size;
+  const Field* eg = b->tb.opts.eg_n ? &b->fields[F_env_geom] : nullptr;
+  a.eg_data = eg ? (const T*)eg->dev : nullptr; a.eg_slot = eg ? b->d_eg_slot : nullptr;
+  a.geom_type = r->d_type; a.geom_body = r->d_body; a.list = r->d_list;
+  a.B = b->B; a.ngeom = r->ngeom; a.nlist = r->nlist; a.cutoff = (T)r->cutoff;
+  a.nray = nray; a.bodyexclude = bex; a.bodyexclude_per_ray = per_ray; a.pnt = (const T*)pnt; a.vec = (const T*)vec;
+  a.bodyexclude_dev = bex_dev;
+  a.nscan = r->nscan; a.ndir = r->ndir; a.scans = (const RayScan<T>*)r->d_scans; a.dirs = (const T*)r->d_dirs;
+  a.dist = (T*)dist; a.geomid = geomid; a.normal = (T*)normal;
+  const int rc = launch_rays(a, scan, stream);
+  if (rc) return fail(rc == -1 ? "rays: the launch grid does not fit" : "rays: launch failed", -2);
+  return 0;
+}
+static int rays_check_mask(dmc_rays* r, int need) {
+  dmc_batch* b = r->b;
+  if ((b->outmask & b->launched_mask & need) != need)
+    return fail("rays: the batch's output mask excludes arrays the rays read (geom / xpos / xmat / site), or "
+                "did when the last step / forward launch ran (or none has run yet): the poses in device memory would be stale", -3);
+  return 0;
+}
+extern "C" int dmc_rays_cast(dmc_rays* r, int nray, const void* pnt_dev, const void* vec_dev, int bodyexclude,
+                             const int32_t* bodyexclude_dev, int bodyexclude_per_ray, void* dist_out, int32_t* geomid_out,
+                             void* normal_out, void* hip_stream) {
+  if (!r) return fail("null rays");
+  if (!pnt_dev || !vec_dev) return fail("rays cast: null input array");
+  if (!dist_out && !geomid_out && !normal_out) return fail("rays cast: nothing asked for");
+  if (nray < 1) return fail("rays cast: the number of rays must be positive");
+  if (!bodyexclude_dev && (bodyexclude < -1 || bodyexclude >= r->b->model->hm.nbody)) return fail("rays cast: bodyexclude out of range");
+  if (int rc = rays_check_mask(r, OUT_GEOM)) return rc;
+  dmc_batch* b = r->b;
+  HIP_TRY(hipSetDevice(b->device));
+  return b->precision == 64
+      ? rays_launch_t<double>(r, false, nray, pnt_dev, vec_dev, bodyexclude, bodyexclude_dev, bodyexclude_per_ray ? 1 : 0, dist_out, geomid_out, normal_out, hip_stream)
+      : rays_launch_t<float>(r, false, nray, pnt_dev, vec_dev, bodyexclude, bodyexclude_dev, bodyexclude_per_ray ? 1 : 0, dist_out, geomid_out, normal_out, hip_stream);
+}
+extern "C" int dmc_rays_scan(dmc_rays* r, void* dist_out, int32_t* geomid_out, void* normal_out, void* hip_stream) {
+  if (!r) return fail("null rays");
+  if (!r->nscan) return fail("rays scan: no scan was added");
+  if (!dist_out && !geomid_out && !normal_out) return fail("rays scan: nothing asked for");
+  if (int rc = rays_check_mask(r, OUT_GEOM | r->scan_mask)) return rc;
+  dmc_batch* b = r->b;
+  HIP_TRY(hipSetDevice(b->device));
+  return b->precision == 64 ? rays_launch_t<double>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream)
+                            : rays_launch_t<float>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream);
+}

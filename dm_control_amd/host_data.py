@@ -479,3 +479,100 @@ def subtree_vel(c, cvel, subtree_com, xipos, ximat=None):
   # sum_b [I w + m (x - X) x (v - V)] = sum_b [I w + m x x v] - M X x V   (X, V: the subtree's centre of mass and its velocity)
   own = spin + mass[:, None] * cross(xipos, lin)
   return vsub, sub @ own - msub[:, None] * cross(subtree_com, vsub)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mj_ray on the host: one environment, numpy.  The device form is csrc/ray_core.h (rays.BatchRays); the rules are stated
+# once, in PARITY_ASSUMPTIONS.md rows 58-60.
+# ---------------------------------------------------------------------------------------------------------------------
+_RAY_TYPES = tuple(C['DMC_GEOM_' + n] for n in ('PLANE', 'SPHERE', 'CAPSULE', 'ELLIPSOID', 'CYLINDER', 'BOX'))
+
+
+def _ray_roots(q, v, r2):
+  """Roots x0 <= x1 of |q + x v|^2 = r2 through the point of closest approach, or None."""
+  a = float(v @ v)
+  if a < MINVAL:
+    return None
+  t0 = -float(q @ v) / a
+  p = q + t0 * v
+  cc = float(p @ p) - r2
+  if cc > 0:
+    return None
+  h = np.sqrt(-cc / a)
+  return t0 - h, t0 + h
+
+
+def _ray_primitive(gtype, s, lp, lv):
+  """Nearest x >= 0 of lp + x lv on one primitive in its own frame, or -1."""
+  PLANE, SPHERE, CAPSULE, ELLIPSOID, CYLINDER, BOX = _RAY_TYPES
+  cands = []
+  if gtype == PLANE:
+    if lv[2] > -MINVAL:
+      return -1.0
+    x = -lp[2] / lv[2]
+    p = lp + x * lv
+    ok = x >= 0 and (s[0] <= 0 or abs(p[0]) <= s[0]) and (s[1] <= 0 or abs(p[1]) <= s[1])
+    return float(x) if ok else -1.0
+  if gtype == SPHERE:
+    cands = list(_ray_roots(lp, lv, s[0] * s[0]) or ())
+  elif gtype == ELLIPSOID:
+    cands = list(_ray_roots(lp / s, lv / s, 1.0) or ())
+  elif gtype in (CAPSULE, CYLINDER):
+    for x in _ray_roots(lp[:2], lv[:2], s[0] * s[0]) or ():
+      if abs(lp[2] + x * lv[2]) <= s[1]:
+        cands.append(x)
+    for sg in (1.0, -1.0):
+      if gtype == CAPSULE:
+        for x in _ray_roots(lp - [0, 0, sg * s[1]], lv, s[0] * s[0]) or ():
+          if sg * (lp[2] + x * lv[2]) >= s[1]:
+            cands.append(x)
+      elif abs(lv[2]) >= MINVAL:
+        x = (sg * s[1] - lp[2]) / lv[2]
+        p = lp + x * lv
+        if p[0] * p[0] + p[1] * p[1] <= s[0] * s[0]:
+          cands.append(x)
+  elif gtype == BOX:
+    for ax in range(3):
+      if abs(lv[ax]) < MINVAL:
+        continue
+      for sg in (-1.0, 1.0):
+        x = (sg * s[ax] - lp[ax]) / lv[ax]
+        p = lp + x * lv
+        if all(abs(p[k]) <= s[k] for k in range(3) if k != ax):
+          cands.append(x)
+  cands = [float(x) for x in cands if x >= 0]
+  return min(cands) if cands else -1.0
+
+
+def ray_filter(c, geomgroup=None, flg_static=1):
+  """(ngeom) bool: the geoms a ray can hit at all -- primitives (meshes and height fields are scenery), visible (the
+  compiler's geom_invisible: alpha 0 on the geom or its material), their group's flag set (groups clamped to 0..5;
+  geomgroup None: every group), and, with flg_static 0, not on a body welded to the world."""
+  ok = np.isin(np.asarray(c.geom_type), _RAY_TYPES) & ~np.asarray(c.geom_invisible, dtype=bool)
+  if geomgroup is not None:
+    flags = np.asarray(geomgroup).reshape(-1)
+    if flags.size != 6:
+      raise ValueError('geomgroup must hold six flags (or be None)')
+    ok &= flags[np.clip(np.asarray(c.geom_group, dtype=np.int64), 0, 5)] != 0
+  if not flg_static:
+    ok &= np.asarray(c.body_weldid)[np.asarray(c.geom_bodyid)] != 0
+  return ok
+
+
+def ray_cast(c, geom_xpos, geom_xmat, geom_size, pnt, vec, geomgroup=None, flg_static=1, bodyexclude=-1):
+  """mj_ray for one environment: (x, geom id) of the nearest hit of pnt + x vec, x >= 0 in units of |vec|; (-1, -1) when
+  nothing is hit.  geom_xpos (ngeom, 3), geom_xmat (ngeom, 9), geom_size (ngeom, 3): the poses and sizes in force."""
+  gpos = np.asarray(geom_xpos, dtype=np.float64).reshape(-1, 3)
+  gmat = np.asarray(geom_xmat, dtype=np.float64).reshape(-1, 3, 3)
+  size = np.asarray(geom_size, dtype=np.float64).reshape(-1, 3)
+  pnt = np.asarray(pnt, dtype=np.float64).reshape(3)
+  vec = np.asarray(vec, dtype=np.float64).reshape(3)
+  ok = ray_filter(c, geomgroup, flg_static)
+  best, gid = -1.0, -1
+  for g in np.nonzero(ok)[0]:
+    if int(c.geom_bodyid[g]) == int(bodyexclude):
+      continue
+    x = _ray_primitive(int(c.geom_type[g]), size[g], gmat[g].T @ (pnt - gpos[g]), gmat[g].T @ vec)
+    if x >= 0 and (gid < 0 or x < best):
+      best, gid = x, int(g)
+  return best, gid

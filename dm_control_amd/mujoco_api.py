@@ -1617,6 +1617,23 @@ def mj_contactForce(m, d, id_, result):
   np.asarray(result).reshape(-1)[:6] = w
 
 
+def mj_ray(m, d, pnt, vec, geomgroup, flg_static, bodyexclude, geomid):
+  """locomotion/tasks/random_goal_maze.py:179-187: the distance x >= 0 (in units of |vec|) along pnt + x vec to the nearest
+  geom that passes the filters, -1 when nothing is hit; the geom's id (or -1) goes to the one-element array `geomid`.
+  geomgroup: six flags or None (every group); flg_static 0 skips the geoms of bodies welded to the world; bodyexclude: a
+  body id, -1 for none.  Meshes and height fields are not hit.  Reads the kinematics as they stand, like mj_jac."""
+  _check(m, d)
+  c = m._c
+  if not d._outputs_valid:
+    d._ensure_forward()
+  get = lambda n, *shape: np.asarray(d._batch.get(n), dtype=np.float64).reshape(shape)
+  x, g = host_data.ray_cast(c, get('geom_xpos', c.ngeom, 3), get('geom_xmat', c.ngeom, 9), c.geom_size, pnt, vec,
+                            geomgroup, flg_static, bodyexclude)
+  if geomid is not None:
+    np.asarray(geomid).reshape(-1)[0] = g
+  return float(x)
+
+
 def mj_objectVelocity(m, d, objtype, objid, res, flg_local):
   """core.py:522: 6D velocity (angular, linear) of a body / xbody / geom / site in the world or the object's own frame."""
   _check(m, d)
