@@ -54,12 +54,19 @@ def _stale(target, sources):
 
 
 def _own_includes(src):
-  """The files a unit's own text includes with quotes, where they exist: a unit is stale against them whether or not its
-  _UNITS entry lists them."""
-  with open(src) as f:
-    names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
-  paths = [os.path.normpath(os.path.join(os.path.dirname(src), n)) for n in names]
-  return [p for p in paths if os.path.exists(p)]
+  """The files a unit's own text includes with quotes, followed through their includes in turn, where they exist: a unit
+  is stale against them whether or not its _UNITS entry lists them.  Generated headers (*.gen.h) are left out: build()
+  names the one its build variant uses, and a production unit is not stale against the profiling layouts."""
+  found, todo = [], [src]
+  while todo:
+    path = todo.pop()
+    with open(path) as f:
+      names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+    for p in (os.path.normpath(os.path.join(os.path.dirname(path), n)) for n in names):
+      if p != src and p not in found and not p.endswith('.gen.h') and os.path.exists(p):
+        found.append(p)
+        todo.append(p)
+  return found
 
 
 # suite models that get model-specialised kernel instantiations: (asset, [lanes...], (nconmax, njmax[, njcon])); the caps

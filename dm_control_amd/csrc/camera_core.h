@@ -131,6 +131,11 @@ CAM_DEV T cam_ray_local(int type, const T* size, const T* lp, const T* lv, int* 
   }
   return -1;      // meshes and height fields are scenery the camera does not draw
 }
+// the primitives cam_ray_local has a closed form for: what the cameras draw and the rays hit
+CAM_DEV bool cam_primitive(int type) {
+  return type == DMC_GEOM_PLANE || type == DMC_GEOM_SPHERE || type == DMC_GEOM_CAPSULE || type == DMC_GEOM_ELLIPSOID ||
+         type == DMC_GEOM_CYLINDER || type == DMC_GEOM_BOX;
+}
 
 // outward unit normal, in the geom's frame, of the point lp + x lv found by cam_ray_local
 template <typename T>

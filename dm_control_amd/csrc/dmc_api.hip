@@ -10,6 +10,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dmc_batch.h"
@@ -113,10 +114,11 @@ struct dmc_batch {
   void* d_task_args = nullptr; int task_on = 0;      // its arguments on the device; whether the next step launches run it
 };
 
-// Device memory of a batch: allocate, optionally zero or fill from `init`, record; a failure leaves *ptr null and the
-// error "hipMalloc <what>: <hip error>".  dmc_batch_destroy frees what is recorded; dev_free releases one buffer early.
-template <typename P>
-static int dev_alloc(dmc_batch* b, P** ptr, size_t bytes, bool zero, const char* what, const void* init = nullptr) {
+// Device memory of an owner (the batch, a camera set, a rays object: whatever holds a `dev_bufs` list): allocate, optionally
+// zero or fill from `init`, record; a failure leaves *ptr null and the error "hipMalloc <what>: <hip error>".  The owner's
+// destroy frees what is recorded (dev_free_all); dev_free releases one buffer early.
+template <class Owner, typename P>
+static int dev_alloc(Owner* b, P** ptr, size_t bytes, bool zero, const char* what, const void* init = nullptr) {
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, bytes);
   if (e == hipSuccess && zero) e = hipMemset(p, 0, bytes);
@@ -126,12 +128,17 @@ static int dev_alloc(dmc_batch* b, P** ptr, size_t bytes, bool zero, const char*
   *ptr = (P*)p;
   return 0;
 }
-template <typename P>
-static void dev_free(dmc_batch* b, P** ptr) {
+template <class Owner, typename P>
+static void dev_free(Owner* b, P** ptr) {
   if (!*ptr) return;
   b->dev_bufs.erase(std::find(b->dev_bufs.begin(), b->dev_bufs.end(), (void*)*ptr));
   (void)hipFree(*ptr);
   *ptr = nullptr;
+}
+template <class Owner>
+static void dev_free_all(Owner* b) {
+  for (void* p : b->dev_bufs) (void)hipFree(p);
+  b->dev_bufs.clear();
 }
 
 extern "C" const char* dmc_last_error(void) { return g_err.c_str(); }
@@ -407,7 +414,7 @@ extern "C" void dmc_batch_destroy(dmc_batch* b) {
   (void)hipSetDevice(b->device);
   if (b->prof) prof_free(b->prof);
   if (b->xfer) xfer_free(b->xfer);
-  for (void* p : b->dev_bufs) (void)hipFree(p);
+  dev_free_all(b);
   delete b;
 }
 
@@ -1381,8 +1388,32 @@ extern "C" int dmc_batch_prof_get(dmc_batch* b, double* dst, int* n) {
 
 // ---- batched ray-cast cameras (camera_core.h, camera_kernels.hip) ----------------------------------------------
 #include "camera_core.h"
+
+// ---- what the add-on units of a batch (cameras, rays) share ------------------------------------------------------
+// f(T()) with the batch's real type: `by_precision(b, [&](auto t) { using T = decltype(t); ... })`
+template <class F>
+static auto by_precision(const dmc_batch* b, F&& f) { return b->precision == 64 ? f(double()) : f(float()); }
+// The batch's poses and geometry as a unit's kernel reads them: the members CamArgs and RayArgs share by name.
+template <class Args>
+static void fill_pose_args(const dmc_batch* b, Args* a) {
+  using P = decltype(a->geom_xpos);      // const T*
+  a->geom_xpos = (P)b->fields[F_geom_xpos].dev; a->geom_xmat = (P)b->fields[F_geom_xmat].dev;
+  a->xpos = (P)b->fields[F_xpos].dev; a->xmat = (P)b->fields[F_xmat].dev;
+  a->geom_size = (P)b->d_mr + b->tb.L.mr_geom_size;
+  const Field* eg = b->tb.opts.eg_n ? &b->fields[F_env_geom] : nullptr;
+  a->eg_data = eg ? (P)eg->dev : nullptr; a->eg_slot = eg ? b->d_eg_slot : nullptr;
+  a->B = b->B;
+}
+// 0 when the derived arrays of `need` (OUT_*) in device memory are those of the last step / forward launch, else -3
+static int poses_fresh(const dmc_batch* b, int need, const char* who) {
+  if ((b->outmask & b->launched_mask & need) == need) return 0;
+  return fail(std::string(who) + ": the batch's output mask excludes arrays it reads (geom / xpos / xmat / subtree_com / site), or "
+              "did when the last step / forward launch ran (or none has run yet): the poses in device memory would be stale", -3);
+}
+
 struct dmc_camera {
   dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
   int ncam, H, W, ngeom, nmat, need_mask, cull, pretransform;
   double near_, far_, ambient, diffuse, bg[3];
   std::vector<int> matid;
@@ -1416,7 +1447,8 @@ extern "C" int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* 
     else need |= OUT_XPOS | OUT_XMAT | (s.mode == CAM_TARGETBODYCOM ? OUT_SUBTREE_COM : 0);
   }
   if (!(opt->near_m >= 0) || !(opt->far_m > opt->near_m)) return fail("camera clip range: need 0 <= near < far");
-  dmc_camera* c = new dmc_camera();
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_camera* c = new dmc_camera();      // (zeroed)
   c->b = b; c->ncam = ncam; c->H = height; c->W = width; c->ngeom = m.ngeom; c->nmat = opt->nmat; c->need_mask = need;
   c->cull = 1; c->pretransform = 1;
   c->near_ = opt->near_m; c->far_ = opt->far_m; c->ambient = opt->ambient; c->diffuse = opt->diffuse;
@@ -1426,48 +1458,28 @@ extern "C" int dmc_camera_create(dmc_batch* b, int ncam, const dmc_camera_spec* 
   for (int g = 0; g < m.ngeom; g++) {
     type[g] = m.geom_type[g];
     const int grp = opt->geom_group ? opt->geom_group[g] : 0;
-    const bool drawn = type[g] == DMC_GEOM_PLANE || type[g] == DMC_GEOM_SPHERE || type[g] == DMC_GEOM_CAPSULE ||
-                       type[g] == DMC_GEOM_ELLIPSOID || type[g] == DMC_GEOM_CYLINDER || type[g] == DMC_GEOM_BOX;
-    skip[g] = !drawn || m.geom_invisible[g] || grp < 0 || grp > 30 || !((opt->group_mask >> grp) & 1);
+    skip[g] = !cam_primitive(type[g]) || m.geom_invisible[g] || grp < 0 || grp > 30 || !((opt->group_mask >> grp) & 1);
     if (opt->geom_matid && opt->geom_matid[g] >= 0) {
       if (opt->geom_matid[g] >= opt->nmat) { delete c; return fail("geom_matid out of range"); }
       c->matid[g] = opt->geom_matid[g];
     }
   }
-  c->d_cams = nullptr; c->d_type = nullptr; c->d_skip = nullptr; c->d_color = nullptr;
-  c->d_mat = nullptr; c->tex_on = 0; c->tex_filter = 0; c->sky = 0;
-  hipError_t e = hipSetDevice(b->device);
   const size_t ni = sizeof(int)*type.size();
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_type, ni);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_skip, ni);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_color, sizeof(float)*3*type.size());
-  if (e == hipSuccess) e = hipMemset(c->d_color, 0, sizeof(float)*3*type.size());
-  if (e == hipSuccess) e = hipMemcpy(c->d_type, type.data(), ni, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->d_skip, skip.data(), ni, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    if (b->precision == 64) {
-      std::vector<CamDev<double>> d(ncam);
-      for (int i = 0; i < ncam; i++) cam_spec_to_dev(specs[i], height, &d[i]);
-      e = hipMalloc(&c->d_cams, sizeof(d[0])*ncam);
-      if (e == hipSuccess) e = hipMemcpy(c->d_cams, d.data(), sizeof(d[0])*ncam, hipMemcpyHostToDevice);
-    } else {
-      std::vector<CamDev<float>> d(ncam);
-      for (int i = 0; i < ncam; i++) cam_spec_to_dev(specs[i], height, &d[i]);
-      e = hipMalloc(&c->d_cams, sizeof(d[0])*ncam);
-      if (e == hipSuccess) e = hipMemcpy(c->d_cams, d.data(), sizeof(d[0])*ncam, hipMemcpyHostToDevice);
-    }
-  }
-  if (e != hipSuccess) { dmc_camera_destroy(c); return fail(std::string("camera create: ") + hipGetErrorString(e), -2); }
+  int rc = dev_alloc(c, &c->d_type, ni, false, "camera geom types", type.data());
+  rc = rc ? rc : dev_alloc(c, &c->d_skip, ni, false, "camera geom mask", skip.data());
+  rc = rc ? rc : dev_alloc(c, &c->d_color, sizeof(float)*3*type.size(), true, "camera geom colours");
+  rc = rc ? rc : by_precision(b, [&](auto t) {
+    std::vector<CamDev<decltype(t)>> d(ncam);
+    for (int i = 0; i < ncam; i++) cam_spec_to_dev(specs[i], height, &d[i]);
+    return dev_alloc(c, &c->d_cams, sizeof(d[0])*ncam, false, "cameras", d.data());
+  });
+  if (rc) { dmc_camera_destroy(c); return rc; }
   *out = c;
   return 0;
 }
 extern "C" void dmc_camera_destroy(dmc_camera* c) {
   if (!c) return;
-  if (c->d_cams) (void)hipFree(c->d_cams);
-  if (c->d_type) (void)hipFree(c->d_type);
-  if (c->d_skip) (void)hipFree(c->d_skip);
-  if (c->d_color) (void)hipFree(c->d_color);
-  if (c->d_mat) (void)hipFree(c->d_mat);
+  dev_free_all(c);
   delete c;
 }
 extern "C" int dmc_camera_set_colors(dmc_camera* c, const double* geom_rgba, const double* mat_rgba) {
@@ -1496,7 +1508,7 @@ static int upload_materials(dmc_camera* c, const dmc_camera_material* mats) {
     for (int k = 0; k < 2; k++) m.rep[k] = (T)s.texrepeat[k];
     for (int k = 0; k < 3; k++) { m.rgb1[k] = (float)s.rgb1[k]; m.rgb2[k] = (float)s.rgb2[k]; m.markrgb[k] = (float)s.markrgb[k]; }
   }
-  if (!c->d_mat) HIP_TRY(hipMalloc(&c->d_mat, sizeof(d[0])*d.size()));
+  if (!c->d_mat) return dev_alloc(c, &c->d_mat, sizeof(d[0])*d.size(), false, "camera materials", d.data());
   HIP_TRY(hipMemcpy(c->d_mat, d.data(), sizeof(d[0])*d.size(), hipMemcpyHostToDevice));
   return 0;
 }
@@ -1519,13 +1531,11 @@ extern "C" int dmc_camera_set_materials(dmc_camera* c, const dmc_camera_material
     if (s.width < 1 || s.height < 1 || s.width > (1 << 24) || s.height > (1 << 24)) return fail("camera materials: a texture needs 1 <= width, height <= 2^24 texels");
     const int type = hm.geom_type[g];
     if ((s.mapping == CAM_MAP_PLANE) != (type == DMC_GEOM_PLANE)) return fail("camera materials: a 2d texture maps onto planes and a cube texture onto solids only");
-    if (s.mapping == CAM_MAP_CUBE && type != DMC_GEOM_SPHERE && type != DMC_GEOM_CAPSULE && type != DMC_GEOM_ELLIPSOID &&
-        type != DMC_GEOM_CYLINDER && type != DMC_GEOM_BOX) return fail("camera materials: a cube texture on a geom the camera does not draw");
+    if (s.mapping == CAM_MAP_CUBE && !cam_primitive(type)) return fail("camera materials: a cube texture on a geom the camera does not draw");
   }
   if (sky && (sky->builtin != CAM_TEX_FLAT && sky->builtin != CAM_TEX_GRADIENT)) return fail("camera materials: the skybox is flat or gradient");
   HIP_TRY(hipSetDevice(c->b->device));
-  const int rc = c->b->precision == 64 ? upload_materials<double>(c, per_geom) : upload_materials<float>(c, per_geom);
-  if (rc) return rc;
+  if (int rc = by_precision(c->b, [&](auto t) { return upload_materials<decltype(t)>(c, per_geom); })) return rc;
   c->mat_rgba_own.assign(4*(size_t)std::max(1, c->ngeom), (double)NAN);
   for (int g = 0; g < c->ngeom; g++) if (per_geom[g].has_rgba) for (int k = 0; k < 4; k++) c->mat_rgba_own[4*g + k] = per_geom[g].rgba[k];
   c->sky = sky ? 1 + sky->builtin : 0;
@@ -1539,23 +1549,15 @@ extern "C" int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform) 
   c->pretransform = pretransform ? 1 : 0;
   return 0;
 }
-static int launch_cam(const CamArgs<float>& a, void* s) { return launch_camera_f32(a, s); }
-static int launch_cam(const CamArgs<double>& a, void* s) { return launch_camera_f64(a, s); }
-static int launch_cam_tex(const CamArgs<float>& a, const CamTexArgs<float>& t, void* s) { return launch_camera_tex_f32(a, t, s); }
-static int launch_cam_tex(const CamArgs<double>& a, const CamTexArgs<double>& t, void* s) { return launch_camera_tex_f64(a, t, s); }
 template <typename T>
 static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void* seg, void* stream) {
   dmc_batch* b = c->b;
   CamArgs<T> a;
-  a.geom_xpos = (const T*)b->fields[F_geom_xpos].dev; a.geom_xmat = (const T*)b->fields[F_geom_xmat].dev;
-  a.xpos = (const T*)b->fields[F_xpos].dev; a.xmat = (const T*)b->fields[F_xmat].dev;
+  fill_pose_args(b, &a);
   a.subtree_com = (const T*)b->fields[F_subtree_com].dev;
-  a.geom_size = (const T*)b->d_mr + b->tb.L.mr_geom_size;
-  const Field* eg = b->tb.opts.eg_n ? &b->fields[F_env_geom] : nullptr;
-  a.eg_data = eg ? (const T*)eg->dev : nullptr; a.eg_slot = eg ? b->d_eg_slot : nullptr;
   a.geom_type = c->d_type; a.geom_skip = c->d_skip; a.geom_color = c->d_color;
   a.cams = (const CamDev<T>*)c->d_cams;
-  a.B = b->B; a.ngeom = c->ngeom; a.ncam = c->ncam; a.H = c->H; a.W = c->W; a.cull = c->cull; a.pretransform = c->pretransform;
+  a.ngeom = c->ngeom; a.ncam = c->ncam; a.H = c->H; a.W = c->W; a.cull = c->cull; a.pretransform = c->pretransform;
   a.near_ = (T)c->near_; a.far_ = (T)c->far_; a.ambient = (T)c->ambient; a.diffuse = (T)c->diffuse;
   for (int k = 0; k < 3; k++) {
     const double v = std::min(1.0, std::max(0.0, c->bg[k]));
@@ -1569,8 +1571,10 @@ static int camera_render_t(dmc_camera* c, int what, void* rgb, void* depth, void
     CamTexArgs<T> t;
     t.mat = (const CamMat<T>*)c->d_mat; t.filter = c->tex_filter; t.sky = c->sky;
     for (int k = 0; k < 3; k++) { t.sky1[k] = c->sky1[k]; t.sky2[k] = c->sky2[k]; }
-    rc = launch_cam_tex(a, t, stream);
-  } else rc = launch_cam(a, stream);
+    if constexpr (std::is_same_v<T, double>) rc = launch_camera_tex_f64(a, t, stream);
+    else rc = launch_camera_tex_f32(a, t, stream);
+  } else if constexpr (std::is_same_v<T, double>) rc = launch_camera_f64(a, stream);
+  else rc = launch_camera_f32(a, stream);
   if (rc) return fail(rc == -1 ? "camera render: the launch grid does not fit" : "camera render: launch failed", -2);
   return 0;
 }
@@ -1579,13 +1583,9 @@ extern "C" int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, vo
   if (!(what_mask & (CAM_RGB | CAM_DEPTH | CAM_SEG))) return fail("camera render: nothing asked for");
   if (((what_mask & CAM_RGB) && !rgb_dev) || ((what_mask & CAM_DEPTH) && !depth_dev) || ((what_mask & CAM_SEG) && !seg_dev))
     return fail("camera render: null output array");
-  dmc_batch* b = c->b;
-  if ((b->outmask & b->launched_mask & c->need_mask) != c->need_mask)
-    return fail("camera render: the batch's output mask excludes arrays the cameras read (geom / xpos / xmat / subtree_com), or "
-                "did when the last step / forward launch ran (or none has run yet): the poses in device memory would be stale", -3);
-  HIP_TRY(hipSetDevice(b->device));
-  return b->precision == 64 ? camera_render_t<double>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream)
-                            : camera_render_t<float>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream);
+  if (int rc = poses_fresh(c->b, c->need_mask, "camera render")) return rc;
+  HIP_TRY(hipSetDevice(c->b->device));
+  return by_precision(c->b, [&](auto t) { return camera_render_t<decltype(t)>(c, what_mask, rgb_dev, depth_dev, seg_dev, hip_stream); });
 }
 
 // ---- batched ray casts (ray_core.h, ray_kernels.hip; include/dmc_ray.h) ------------------------------------------
@@ -1593,6 +1593,7 @@ extern "C" int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, vo
 #include "ray_core.h"
 struct dmc_rays {
   dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
   int ngeom, nlist, nscan, ndir, scan_mask;
   double cutoff;
   int *d_type, *d_body, *d_list;
@@ -1600,7 +1601,6 @@ struct dmc_rays {
   std::vector<dmc::RayScan<double>> scans;
   std::vector<double> dirs;
 };
-static void rays_free(void** p) { if (*p) (void)hipFree(*p); *p = nullptr; }
 extern "C" int dmc_rays_create(dmc_batch* b, const dmc_rays_options* opt, dmc_rays** out) {
   if (!b || !opt || !out) return fail("null argument");
   const HostModel& m = b->model->hm;
@@ -1612,33 +1612,26 @@ extern "C" int dmc_rays_create(dmc_batch* b, const dmc_rays_options* opt, dmc_ra
     body[g] = m.geom_bodyid[g];
     if (body[g] < 0 || body[g] >= m.nbody) return fail("rays: geom body out of range");
     const int grp = std::min(5, std::max(0, opt->geom_group[g]));
-    const bool solid = type[g] == DMC_GEOM_PLANE || type[g] == DMC_GEOM_SPHERE || type[g] == DMC_GEOM_CAPSULE ||
-                       type[g] == DMC_GEOM_ELLIPSOID || type[g] == DMC_GEOM_CYLINDER || type[g] == DMC_GEOM_BOX;
-    if (!solid || m.geom_invisible[g] || (opt->has_geomgroup && !opt->geomgroup[grp]) ||
+    if (!cam_primitive(type[g]) || m.geom_invisible[g] || (opt->has_geomgroup && !opt->geomgroup[grp]) ||
         (!opt->flg_static && m.body_weldid[body[g]] == 0)) continue;
     list.push_back(g);
   }
-  dmc_rays* r = new dmc_rays();
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_rays* r = new dmc_rays();      // (zeroed)
   r->b = b; r->ngeom = m.ngeom; r->nlist = (int)list.size(); r->nscan = 0; r->ndir = 0; r->scan_mask = 0;
   r->cutoff = (opt->cutoff > 0 && opt->cutoff < 1e30) ? opt->cutoff : (double)INFINITY;
-  r->d_type = nullptr; r->d_body = nullptr; r->d_list = nullptr; r->d_scans = nullptr; r->d_dirs = nullptr;
   list.resize(std::max<size_t>(1, list.size()), 0);
-  hipError_t e = hipSetDevice(b->device);
   const size_t ni = sizeof(int)*type.size();
-  if (e == hipSuccess) e = hipMalloc((void**)&r->d_type, ni);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->d_body, ni);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->d_list, sizeof(int)*list.size());
-  if (e == hipSuccess) e = hipMemcpy(r->d_type, type.data(), ni, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(r->d_body, body.data(), ni, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(r->d_list, list.data(), sizeof(int)*list.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { dmc_rays_destroy(r); return fail(std::string("rays create: ") + hipGetErrorString(e), -2); }
+  int rc = dev_alloc(r, &r->d_type, ni, false, "rays geom types", type.data());
+  rc = rc ? rc : dev_alloc(r, &r->d_body, ni, false, "rays geom bodies", body.data());
+  rc = rc ? rc : dev_alloc(r, &r->d_list, sizeof(int)*list.size(), false, "rays geom list", list.data());
+  if (rc) { dmc_rays_destroy(r); return rc; }
   *out = r;
   return 0;
 }
 extern "C" void dmc_rays_destroy(dmc_rays* r) {
   if (!r) return;
-  rays_free((void**)&r->d_type); rays_free((void**)&r->d_body); rays_free((void**)&r->d_list);
-  rays_free(&r->d_scans); rays_free(&r->d_dirs);
+  dev_free_all(r);
   delete r;
 }
 extern "C" int dmc_rays_info(const dmc_rays* r, int* info) {
@@ -1657,13 +1650,10 @@ static int rays_upload_scans(dmc_rays* r) {
   }
   std::vector<T> d(r->dirs.begin(), r->dirs.end());
   void *ds = nullptr, *dd = nullptr;
-  hipError_t e = hipMalloc(&ds, sizeof(s[0])*s.size());
-  if (e == hipSuccess) e = hipMalloc(&dd, sizeof(T)*d.size());
-  if (e == hipSuccess) e = hipMemcpy(ds, s.data(), sizeof(s[0])*s.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dd, d.data(), sizeof(T)*d.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { rays_free(&ds); rays_free(&dd); return fail(std::string("rays add_scan: ") + hipGetErrorString(e), -2); }
+  if (dev_alloc(r, &ds, sizeof(s[0])*s.size(), false, "rays scans", s.data()) ||
+      dev_alloc(r, &dd, sizeof(T)*d.size(), false, "rays scan directions", d.data())) { dev_free(r, &ds); return -2; }
   HIP_TRY(hipDeviceSynchronize());      // (a launch in flight may still read the tables this replaces)
-  rays_free(&r->d_scans); rays_free(&r->d_dirs);
+  dev_free(r, &r->d_scans); dev_free(r, &r->d_dirs);
   r->d_scans = ds; r->d_dirs = dd;
   return 0;
 }
@@ -1686,40 +1676,28 @@ extern "C" int dmc_rays_add_scan(dmc_rays* r, int frame_type, int frame_id, cons
   r->scans.push_back(s);
   r->dirs.insert(r->dirs.end(), dirs_host, dirs_host + 3*(size_t)ndir);
   HIP_TRY(hipSetDevice(r->b->device));
-  const int rc = r->b->precision == 64 ? rays_upload_scans<double>(r) : rays_upload_scans<float>(r);
-  if (rc) { r->scans.pop_back(); r->dirs.resize(r->dirs.size() - 3*(size_t)ndir); return rc; }
+  if (int rc = by_precision(r->b, [&](auto t) { return rays_upload_scans<decltype(t)>(r); })) { r->scans.pop_back(); r->dirs.resize(r->dirs.size() - 3*(size_t)ndir); return rc; }
   r->nscan = (int)r->scans.size(); r->ndir = ndir;
   r->scan_mask |= frame_type == RAY_FRAME_BODY ? (OUT_XPOS | OUT_XMAT) : frame_type == RAY_FRAME_SITE ? OUT_SITE : 0;
   return 0;
 }
-static int launch_rays(const RayArgs<float>& a, bool scan, void* s) { return scan ? launch_ray_scan_f32(a, s) : launch_ray_cast_f32(a, s); }
-static int launch_rays(const RayArgs<double>& a, bool scan, void* s) { return scan ? launch_ray_scan_f64(a, s) : launch_ray_cast_f64(a, s); }
 template <typename T>
 static int rays_launch_t(dmc_rays* r, bool scan, int nray, const void* pnt, const void* vec, int bex, const int32_t* bex_dev,
                          int per_ray, void* dist, int32_t* geomid, void* normal, void* stream) {
   dmc_batch* b = r->b;
   RayArgs<T> a;
-  a.geom_xpos = (const T*)b->fields[F_geom_xpos].dev; a.geom_xmat = (const T*)b->fields[F_geom_xmat].dev;
-  a.xpos = (const T*)b->fields[F_xpos].dev; a.xmat = (const T*)b->fields[F_xmat].dev;
+  fill_pose_args(b, &a);
   a.site_xpos = (const T*)b->fields[F_site_xpos].dev; a.site_xmat = (const T*)b->fields[F_site_xmat].dev;
-  a.geom_size = (const T*)b->d_mr + b->tb.L.mr_geom_size;
-  const Field* eg = b->tb.opts.eg_n ? &b->fields[F_env_geom] : nullptr;
-  a.eg_data = eg ? (const T*)eg->dev : nullptr; a.eg_slot = eg ? b->d_eg_slot : nullptr;
   a.geom_type = r->d_type; a.geom_body = r->d_body; a.list = r->d_list;
-  a.B = b->B; a.ngeom = r->ngeom; a.nlist = r->nlist; a.cutoff = (T)r->cutoff;
+  a.ngeom = r->ngeom; a.nlist = r->nlist; a.cutoff = (T)r->cutoff;
   a.nray = nray; a.bodyexclude = bex; a.bodyexclude_per_ray = per_ray; a.pnt = (const T*)pnt; a.vec = (const T*)vec;
   a.bodyexclude_dev = bex_dev;
   a.nscan = r->nscan; a.ndir = r->ndir; a.scans = (const RayScan<T>*)r->d_scans; a.dirs = (const T*)r->d_dirs;
   a.dist = (T*)dist; a.geomid = geomid; a.normal = (T*)normal;
-  const int rc = launch_rays(a, scan, stream);
+  int rc;
+  if constexpr (std::is_same_v<T, double>) rc = scan ? launch_ray_scan_f64(a, stream) : launch_ray_cast_f64(a, stream);
+  else rc = scan ? launch_ray_scan_f32(a, stream) : launch_ray_cast_f32(a, stream);
   if (rc) return fail(rc == -1 ? "rays: the launch grid does not fit" : "rays: launch failed", -2);
-  return 0;
-}
-static int rays_check_mask(dmc_rays* r, int need) {
-  dmc_batch* b = r->b;
-  if ((b->outmask & b->launched_mask & need) != need)
-    return fail("rays: the batch's output mask excludes arrays the rays read (geom / xpos / xmat / site), or "
-                "did when the last step / forward launch ran (or none has run yet): the poses in device memory would be stale", -3);
   return 0;
 }
 extern "C" int dmc_rays_cast(dmc_rays* r, int nray, const void* pnt_dev, const void* vec_dev, int bodyexclude,
@@ -1730,20 +1708,19 @@ extern "C" int dmc_rays_cast(dmc_rays* r, int nray, const void* pnt_dev, const v
   if (!dist_out && !geomid_out && !normal_out) return fail("rays cast: nothing asked for");
   if (nray < 1) return fail("rays cast: the number of rays must be positive");
   if (!bodyexclude_dev && (bodyexclude < -1 || bodyexclude >= r->b->model->hm.nbody)) return fail("rays cast: bodyexclude out of range");
-  if (int rc = rays_check_mask(r, OUT_GEOM)) return rc;
-  dmc_batch* b = r->b;
-  HIP_TRY(hipSetDevice(b->device));
-  return b->precision == 64
-      ? rays_launch_t<double>(r, false, nray, pnt_dev, vec_dev, bodyexclude, bodyexclude_dev, bodyexclude_per_ray ? 1 : 0, dist_out, geomid_out, normal_out, hip_stream)
-      : rays_launch_t<float>(r, false, nray, pnt_dev, vec_dev, bodyexclude, bodyexclude_dev, bodyexclude_per_ray ? 1 : 0, dist_out, geomid_out, normal_out, hip_stream);
+  if (int rc = poses_fresh(r->b, OUT_GEOM, "rays")) return rc;
+  HIP_TRY(hipSetDevice(r->b->device));
+  return by_precision(r->b, [&](auto t) {
+    return rays_launch_t<decltype(t)>(r, false, nray, pnt_dev, vec_dev, bodyexclude, bodyexclude_dev, bodyexclude_per_ray ? 1 : 0, dist_out, geomid_out, normal_out, hip_stream);
+  });
 }
 extern "C" int dmc_rays_scan(dmc_rays* r, void* dist_out, int32_t* geomid_out, void* normal_out, void* hip_stream) {
   if (!r) return fail("null rays");
   if (!r->nscan) return fail("rays scan: no scan was added");
   if (!dist_out && !geomid_out && !normal_out) return fail("rays scan: nothing asked for");
-  if (int rc = rays_check_mask(r, OUT_GEOM | r->scan_mask)) return rc;
-  dmc_batch* b = r->b;
-  HIP_TRY(hipSetDevice(b->device));
-  return b->precision == 64 ? rays_launch_t<double>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream)
-                            : rays_launch_t<float>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream);
+  if (int rc = poses_fresh(r->b, OUT_GEOM | r->scan_mask, "rays")) return rc;
+  HIP_TRY(hipSetDevice(r->b->device));
+  return by_precision(r->b, [&](auto t) {
+    return rays_launch_t<decltype(t)>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream);
+  });
 }

@@ -93,6 +93,8 @@ struct dmc_ik {
   void* d_reals = nullptr;
 };
 
+// On purpose not on dmc_api.hip's scaffold of the camera and ray units (dev_alloc, poses_fresh, by_precision): these entry
+// points see the batch through its public ABI alone, with their own error channel, DeviceScope and pointer checks.
 static thread_local std::string g_ik_err;
 static int ik_fail(const std::string& msg, int code = -1) { g_ik_err = msg; return code; }
 extern "C" const char* dmc_ik_last_error(void) { return g_ik_err.c_str(); }

@@ -21,18 +21,17 @@ launch wrote; geom sizes are the ones the step kernel uses (after `set_model_rea
 `set_env_geoms` geoms).
 """
 import ctypes
-import logging
 import math
 
 import numpy as np
 
 from dm_control_amd import _native
+from dm_control_amd import _unit
 from dm_control_amd import camera as camera_lib
 from dm_control_amd import mjcf_compiler
 
 FRAME_WORLD, FRAME_BODY, FRAME_SITE, FRAME_GEOM = 0, 1, 2, 3
 _FRAME_KEYS = {'body': FRAME_BODY, 'site': FRAME_SITE, 'geom': FRAME_GEOM}
-_HIT_TYPES = (0, 2, 3, 4, 5, 6)      # plane, sphere, capsule, ellipsoid, cylinder, box
 
 
 class _Options(ctypes.Structure):      # dmc_rays_options
@@ -114,16 +113,18 @@ def broadcast_rays(pnt, vec, batch_size, dtype=None, device=None):
   return tuple(t.expand(batch_size, nray, 3).contiguous() for t in out)
 
 
-class BatchRays:
+class BatchRays(_unit.BatchUnit):
   """Ray casts for every environment of a batch; see the module docstring for what is hit.
 
   physics_or_batch: a `BatchedPhysics`, or anything holding one as `.batch` (Physics) or `.physics`.
   geomgroup: six flags or None (every group); flg_static: False skips the geoms of bodies welded to the world;
   cutoff: metres, farther hits become misses (None: no cutoff).  These are fixed for the object's life.
   """
+  _DESTROY = 'dmc_rays_destroy'
+  _OUT_ERROR = 'out: expected a contiguous %s tensor of shape %s on %s'
 
   def __init__(self, physics_or_batch, geomgroup=None, flg_static=True, cutoff=None):
-    batch = camera_lib._find_batch(physics_or_batch, 3)      # pylint: disable=protected-access
+    batch = _unit.find_batch(physics_or_batch)
     if batch is None:
       raise TypeError('BatchRays needs a BatchedPhysics (or an object holding one as .batch / .physics / .host_physics)')
     self.batch, self.model = batch, batch.model
@@ -145,12 +146,8 @@ class BatchRays:
     self._group = np.ascontiguousarray(m.geom_group, dtype=np.int32)
     opt.geom_group = self._group.ctypes.data if m.ngeom else None
     opt.ngeom_group = int(m.ngeom)
-    names = m.names.get('geom', [None] * m.ngeom)
     # the gap, as BatchCamera.untextured states its own: these geoms compile as scenery and no ray hits them
-    self.skipped_geoms = [names[g] if names[g] is not None else g for g in range(m.ngeom) if int(m.geom_type[g]) not in _HIT_TYPES]
-    if self.skipped_geoms:
-      logging.getLogger(__name__).info('BatchRays: %d mesh / height-field geoms are not hit: %s', len(self.skipped_geoms),
-                                       self.skipped_geoms)
+    self.skipped_geoms = _unit.skipped_geoms(m, 'BatchRays')
     self._ptr = ctypes.c_void_p()
     _native.check(_native.lib().dmc_rays_create(batch._ptr, ctypes.byref(opt), ctypes.byref(self._ptr)))
     from dm_control_amd.batch import OUT      # pylint: disable=import-outside-toplevel
@@ -158,39 +155,19 @@ class BatchRays:
     self.output_mask = OUT['geom']      # the derived arrays a step launch must write for these rays
     self.scans = []
 
-  def close(self):
-    if getattr(self, '_ptr', None):
-      _native.lib().dmc_rays_destroy(self._ptr)
-      self._ptr = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint: disable=broad-except
-      pass
-
   def info(self):
     a = np.zeros(8, dtype=np.int32)
     _native.check(_native.lib().dmc_rays_info(self._ptr, a.ctypes.data))
     return dict(zip(('B', 'precision', 'geoms', 'nscan', 'ndir', 'cast_block', 'scan_tile', 'scan_pass'), (int(x) for x in a)))
 
   # -- tensors ------------------------------------------------------------------------------------------------------
-  def _torch(self):
-    import torch      # pylint: disable=import-outside-toplevel
-    return torch, torch.device('cuda', self.batch.device_id), torch.float64 if self.batch.precision == 64 else torch.float32
-
   def _outputs(self, shape, normals, out):
-    torch, dev, dt = self._torch()
+    torch, _, dt = self._torch()
     want = [(shape, dt), (shape, torch.int32)] + ([(shape + (3,), dt)] if normals else [])
-    if out is None:
-      return [torch.empty(s, dtype=d, device=dev) for s, d in want]
-    out = list(out)
+    out = [None] * len(want) if out is None else list(out)
     if len(out) != len(want):
       raise ValueError('out must hold %d tensors (dist, geomid%s)' % (len(want), ', normal' if normals else ''))
-    for t, (s, d) in zip(out, want):
-      if tuple(t.shape) != s or t.dtype != d or t.device != dev or not t.is_contiguous():
-        raise ValueError('out: expected a contiguous %s tensor of shape %s on %s' % (d, s, dev))
-    return out
+    return [self._tensor(s, d, o) for (s, d), o in zip(want, out)]
 
   # -- arbitrary rays -----------------------------------------------------------------------------------------------
   def cast(self, pnt, vec, bodyexclude=-1, normals=False, out=None, stream=None):
@@ -215,7 +192,7 @@ class BatchRays:
     _native.check(_native.lib().dmc_rays_cast(self._ptr, R, p.data_ptr(), v.data_ptr(), bex,
                                               bex_t.data_ptr() if bex_t is not None else None, per_ray, res[0].data_ptr(),
                                               res[1].data_ptr(), res[2].data_ptr() if normals else None,
-                                              camera_lib.BatchCamera._stream_handle(stream)))      # pylint: disable=protected-access
+                                              self.stream_handle(stream)))
     return tuple(res)
 
   # -- scans --------------------------------------------------------------------------------------------------------
@@ -249,7 +226,7 @@ class BatchRays:
     shape = (self.batch.batch_size, len(self.scans), self.scans[0]['directions'].shape[0])
     res = self._outputs(shape, normals, out)
     _native.check(_native.lib().dmc_rays_scan(self._ptr, res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr() if normals else None,
-                                              camera_lib.BatchCamera._stream_handle(stream)))      # pylint: disable=protected-access
+                                              self.stream_handle(stream)))
     return tuple(res)
 
   def scan_rays(self, k, xpos, xmat, site_xpos, site_xmat, geom_xpos, geom_xmat):

@@ -13,12 +13,14 @@ to, as a rangefinder skips its site's body (`bodyexclude` overrides).
 import numpy as np
 
 from dm_control_amd import rays as rays_lib
+from dm_control_amd.suite import observation_wrapper
 
 _SCALES = (None, 'tanh')
 
 
-class LidarEnv:
+class LidarEnv(observation_wrapper.ObservationWrapper):
   """An environment whose observations are (or include) a range scan; everything else is the wrapped environment's."""
+  _ONLY = 'lidar_only'
 
   def __init__(self, env, frame, directions, observation_key='lidar', lidar_only=False, cutoff=None, scale=None,
                offset=(0, 0, 0), bodyexclude='frame', **rays_kwargs):
@@ -32,25 +34,11 @@ class LidarEnv:
     n = np.linalg.norm(d, axis=1, keepdims=True)
     if not np.all(n > 0):
       raise ValueError('directions: a direction has zero length')
-    self.env = env
-    self.lidar_only, self.observation_key, self.scale = bool(lidar_only), observation_key, scale
+    super().__init__(env, observation_key, lidar_only)
+    self.scale = scale
     self.rays = rays_lib.BatchRays(env, cutoff=cutoff, **rays_kwargs)
     self.rays.add_scan(frame, d / n, offset=offset, bodyexclude=bodyexclude)
-    batch = self.rays.batch
-    # the step launches must write the poses the rays read; a recorded HIP graph keeps the mask it was captured with
-    need = batch.output_mask | self.rays.output_mask
-    if need != batch.output_mask:
-      batch.set_output_mask(need)
-    if getattr(env, 'output_mask', None) is not None:
-      env.output_mask |= self.rays.output_mask      # (fused_env restores this mask after drawing start states)
-    if hasattr(env, 'invalidate_graph'):
-      env.invalidate_graph()
-    elif getattr(env, '_graph', None) is not None:
-      raise ValueError('wrap the environment before recording its control step into a HIP graph (capture_graph): the '
-                       'recorded launches write the derived arrays of the output mask they were captured with')
-
-  def __getattr__(self, name):
-    return getattr(self.env, name)
+    self._require_outputs(self.rays)
 
   def scan(self):
     """The (B, R) scan of the state in device memory, enqueued on the current stream."""
@@ -60,21 +48,8 @@ class LidarEnv:
       dist = torch.where(dist < 0, torch.ones_like(dist), torch.tanh(dist / self.rays.cutoff))
     return dist
 
-  def _observe(self, result):
-    scan = self.scan()
-    if hasattr(result, '_replace') and hasattr(result, 'observation'):      # a TimeStep (composer)
-      obs = {} if self.lidar_only else dict(result.observation)
-      obs[self.observation_key] = scan
-      return result._replace(observation=obs)
-    if isinstance(result, tuple):      # (obs, reward, done, ...)
-      return ((scan if self.lidar_only else {'state': result[0], self.observation_key: scan}),) + tuple(result[1:])
-    return scan if self.lidar_only else {'state': result, self.observation_key: scan}
-
-  def step(self, action=None):
-    return self._observe(self.env.step(action))
-
-  def reset(self, *args, **kwargs):
-    return self._observe(self.env.reset(*args, **kwargs))
+  def _read(self):
+    return self.scan()
 
 
 def wrap(env, frame, directions, observation_key='lidar', lidar_only=False, cutoff=None, scale=None, **kw):

@@ -18,6 +18,7 @@ import logging
 import numpy as np
 
 from dm_control_amd import _native
+from dm_control_amd import _unit
 from dm_control_amd import host_data
 from dm_control_amd import mjcf_compiler
 
@@ -122,12 +123,13 @@ class _Options(ctypes.Structure):
       [('max_steps', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
-class BatchIK:
+class BatchIK(_unit.BatchUnit):
   """qpos_from_site_pose for every environment of a batch in one launch (include/dmc_ik.h).
 
   `physics`: a `Physics` or a `BatchedPhysics`.  The kinematic chain is read from the compiled model HERE: model edits
   made afterwards (body_pos, site_pos, ... through physics.model / set_model_real) need a new object.  Options are the
   keyword arguments of the reference's function; `tol=None` is 1e-14 on an fp64 batch and `TOL_F32` on an fp32 one."""
+  _DESTROY = 'dmc_ik_destroy'
 
   def __init__(self, physics, site_name, joint_names=None, tol=None, rot_weight=1.0, regularization_threshold=0.1,
                regularization_strength=3e-2, max_update_norm=2.0, progress_thresh=20.0, max_steps=100):
@@ -152,17 +154,6 @@ class BatchIK:
     if L.dmc_ik_create(self.batch._ptr, ctypes.byref(c), ctypes.byref(o), ctypes.byref(self._ptr)) != 0:
       raise _native.NativeError(L.dmc_ik_last_error().decode())
 
-  def close(self):
-    if getattr(self, '_ptr', None):
-      _native.lib().dmc_ik_destroy(self._ptr)
-      self._ptr = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint: disable=broad-except
-      pass
-
   def info(self):
     a = np.zeros(7, dtype=np.int32)
     if _native.lib().dmc_ik_info(self._ptr, a.ctypes.data) != 0:
@@ -183,29 +174,22 @@ class BatchIK:
     device; `success` is `status == 0`.  `qpos=None` starts from the batch's own qpos; `inplace=True` also writes the
     result there (and invalidates the batch's stashes on the stream).  Asynchronous on `stream` (a torch stream or a raw
     handle; default: torch's current stream)."""
-    import torch      # pylint: disable=import-outside-toplevel
     if target_pos is None and target_quat is None:
       raise ValueError(_REQUIRE_TARGET_POS_OR_QUAT)
-    b = self.batch
-    B, nq = b.batch_size, int(self.model.nq)
-    dev = torch.device('cuda', b.device_id)
-    dt = torch.float64 if self.precision == 64 else torch.float32
+    torch, dev, dt = self._torch()
+    B, nq = self.batch.batch_size, int(self.model.nq)
     tp, tq = self._target(target_pos, 3, torch, dev, dt), self._target(target_quat, 4, torch, dev, dt)
     if qpos is not None:
       qpos = torch.as_tensor(qpos, dtype=dt, device=dev) if not isinstance(qpos, torch.Tensor) else qpos.to(device=dev, dtype=dt)
       if tuple(qpos.shape) != (B, nq):
         raise ValueError('qpos must have shape (%d, %d), got %s' % (B, nq, tuple(qpos.shape)))
       qpos = qpos.contiguous()
-    out = dict(qpos=torch.empty((B, nq), dtype=dt, device=dev), err_norm=torch.empty((B,), dtype=dt, device=dev),
-               steps=torch.empty((B,), dtype=torch.int32, device=dev), status=torch.empty((B,), dtype=torch.int32, device=dev))
-    if stream is None:
-      handle = torch.cuda.current_stream(dev).cuda_stream or None
-    else:
-      handle = getattr(stream, 'cuda_stream', stream) or None
+    out = dict(qpos=self._tensor((B, nq), dt), err_norm=self._tensor((B,), dt), steps=self._tensor((B,), torch.int32),
+               status=self._tensor((B,), torch.int32))
     ptr = lambda t: t.data_ptr() if t is not None else None
     L = _native.lib()
     if L.dmc_ik_solve(self._ptr, ptr(tp), ptr(tq), ptr(qpos), int(bool(inplace)), out['qpos'].data_ptr(),
-                      out['err_norm'].data_ptr(), out['steps'].data_ptr(), out['status'].data_ptr(), handle) != 0:
+                      out['err_norm'].data_ptr(), out['steps'].data_ptr(), out['status'].data_ptr(), self.stream_handle(stream)) != 0:
       raise _native.NativeError(L.dmc_ik_last_error().decode())
     self._keep = (tp, tq, qpos)      # (alive until the next solve: the launch is asynchronous)
     return out

@@ -1,9 +1,10 @@
-"""Device assembly of the step kernels of one source tree, hashed: the check that a refactor changes no instruction.
+"""Device assembly of every kernel unit of one source tree, hashed: the check that a refactor changes no instruction.
    python scripts/unit_isa_hash.py <tree> <outdir>      -- prints {unit: sha256} as JSON; the .s files stay in <outdir>
-Units: the three step units of the library (each with its own flags of build.py, plus --cuda-device-only -S) and
-step_kernel_spec.hip for the cheetah at fp32 and fp64, the command being the one specialise.build issues with
-`-shared -o <plugin>` replaced.  Lines that hold the per-compilation `__hip_cuid_<hash>` symbol are dropped before hashing;
-two trees changed no kernel iff all five hashes agree.  No GPU is needed; about 15 CPU-minutes per tree."""
+Units: the three step units of the library and its add-on units camera_kernels, ray_kernels and ik_kernels (each with
+its own flags of build.py, plus --cuda-device-only -S) and step_kernel_spec.hip for the cheetah at fp32 and fp64, the
+command being the one specialise.build issues with `-shared -o <plugin>` replaced.  Lines that hold the per-compilation
+`__hip_cuid_<hash>` symbol are dropped before hashing;
+two trees changed no kernel iff all eight hashes agree.  No GPU is needed; about 15 CPU-minutes per tree."""
 import hashlib, json, os, subprocess, sys, tempfile
 tree, out = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])
 os.makedirs(out, exist_ok=True)
@@ -13,7 +14,7 @@ assert os.path.dirname(B.HERE) == tree, 'dm_control_amd was imported from %s' % 
 B.generate_static_layouts()
 procs = []
 for src, flags, *_ in B._UNITS:
-  if src.startswith('step_kernels_'):
+  if src != 'dmc_api.hip':      # (the host side: no kernel of its own)
     cmd = [B.HIPCC] + B._COMMON + flags + ['--cuda-device-only', '-S', os.path.join(B.CSRC, src), '-o', os.path.join(out, src.replace('.hip', '.s'))]
     procs.append((src.replace('.hip', ''), subprocess.Popen(cmd, stderr=subprocess.DEVNULL)))
 os.environ['DMC_SPEC_CACHE'] = tempfile.mkdtemp()

@@ -1,13 +1,13 @@
 """TEST INFRASTRUCTURE: host build of the camera's texture functions, see tests/emu/camera_texture_emu.cpp."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, 'emu', 'camera_texture_emu.cpp')
-_LIB = os.path.join(_HERE, 'emu', 'libcamera_texture_emu.so')
 _lib = None
 BUILTIN = {'flat': 0, 'checker': 1, 'gradient': 2}
 MARK = {'none': 0, 'random': 0, 'edge': 1, 'cross': 2}
@@ -16,19 +16,7 @@ MARK = {'none': 0, 'random': 0, 'edge': 1, 'cross': 2}
 def lib():
   global _lib
   if _lib is None:
-    root = os.path.dirname(_HERE)
-    deps = [_SRC, os.path.join(root, 'dm_control_amd', 'csrc', 'camera_core.h'), os.path.join(root, 'include', 'dmc_model_layout.h')]
-    stale = lambda: not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in deps)
-    if stale():
-      import fcntl
-      with open(_LIB + '.lock', 'w') as lk:      # (pytest-xdist workers: one builds, the others wait and load)
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if stale():
-          tmp = _LIB + '.%d.tmp' % os.getpid()
-          subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas',
-                                 '-o', tmp, _SRC])
-          os.replace(tmp, _LIB)
-    L = ctypes.CDLL(_LIB)
+    L = host_build.load(_SRC, 'camera_texture_emu')
     vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     L.cam_tex_emu_render.argtypes = [ci, vp, vp, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, cd, cd, cd, cd, vp, vp, vp]
     L.cam_tex_emu_render.restype = None

@@ -1,15 +1,15 @@
 """TEST INFRASTRUCTURE: host build (LPE=1) of the kernel core, see tests/emu/emu.cpp."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
 from dm_control_amd import _layout
 
+import host_build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, 'emu', 'emu.cpp')
-_LIB = os.path.join(_HERE, 'emu', 'libemu.so')
 _lib = None
 
 # the data fields of include/dmc_model_layout.h, in its order: emu_run takes one array per field, in this order
@@ -17,24 +17,13 @@ FIELDS = [n for n, _ in _layout.DATA_REAL_FIELDS]
 IFIELDS = [n for n, _ in _layout.DATA_INT_FIELDS]
 
 
-def lib():
+def lib(src=_SRC, name='emu', **build_args):
+  """The host build, loaded once per module; the arguments of the first call choose it (tests/test_content_dims_cpu.py loads
+  copies of this module on variants of the source)."""
   global _lib
   if _lib is None:
     from dm_control_amd import build
-    deps = [_SRC] + [os.path.join(build.CSRC, f) for f in build.STEP_SOURCES]
-    stale = lambda: not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in deps)
-    if stale():
-      # (pytest-xdist workers may all find it stale at once: one builds under a lock, into a temporary that is moved in
-      # place atomically -- a worker never loads a half-written object)
-      import fcntl
-      with open(_LIB + '.lock', 'w') as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if stale():
-          tmp = _LIB + '.%d.tmp' % os.getpid()
-          subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas',
-                                 '-o', tmp, _SRC])
-          os.replace(tmp, _LIB)
-    L = ctypes.CDLL(_LIB)
+    L = host_build.load(src, name, deps=[os.path.join(build.CSRC, f) for f in build.STEP_SOURCES], **build_args)
     L.emu_last_error.restype = ctypes.c_char_p
     L.emu_create.restype = ctypes.c_void_p
     L.emu_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]

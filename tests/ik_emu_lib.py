@@ -1,33 +1,20 @@
 """TEST INFRASTRUCTURE: host build of the inverse-kinematics core, see tests/emu/ik_emu.cpp."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, 'emu', 'ik_emu.cpp')
-_LIB = os.path.join(_HERE, 'emu', 'libik_emu.so')
 _lib = None
 
 
 def lib():
   global _lib
   if _lib is None:
-    root = os.path.dirname(_HERE)
-    csrc = os.path.join(root, 'dm_control_amd', 'csrc')
-    deps = [_SRC] + [os.path.join(csrc, h) for h in ('ik_core.h', 'step_defs.h', 'step_math.h')] + [os.path.join(root, 'include', 'dmc_model_layout.h')]
-    stale = lambda: not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in deps)
-    if stale():
-      import fcntl
-      with open(_LIB + '.lock', 'w') as lk:      # (pytest-xdist workers: one builds, the others wait and load)
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if stale():
-          tmp = _LIB + '.%d.tmp' % os.getpid()
-          subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas',
-                                 '-o', tmp, _SRC])
-          os.replace(tmp, _LIB)
-    L = ctypes.CDLL(_LIB)
+    L = host_build.load(_SRC, 'ik_emu')
     vp, ci = ctypes.c_void_p, ctypes.c_int
     L.ik_emu_solve.argtypes = [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.ik_emu_pose.argtypes = [vp] * 8

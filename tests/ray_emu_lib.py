@@ -1,34 +1,20 @@
 """TEST INFRASTRUCTURE: host build of the ray unit's per-ray functions, see tests/emu/ray_emu.cpp."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, 'emu', 'ray_emu.cpp')
-_LIB = os.path.join(_HERE, 'emu', 'libray_emu.so')
 _lib = None
 
 
 def lib():
   global _lib
   if _lib is None:
-    root = os.path.dirname(_HERE)
-    csrc = os.path.join(root, 'dm_control_amd', 'csrc')
-    deps = [_SRC, os.path.join(root, 'include', 'dmc_model_layout.h')] + [os.path.join(csrc, h) for h in
-                                                                         ('ray_core.h', 'camera_core.h', 'step_geom.h', 'step_defs.h', 'step_math.h')]
-    stale = lambda: not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in deps)
-    if stale():
-      import fcntl
-      with open(_LIB + '.lock', 'w') as lk:      # (pytest-xdist workers: one builds, the others wait and load)
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if stale():
-          tmp = _LIB + '.%d.tmp' % os.getpid()
-          subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas',
-                                 '-o', tmp, _SRC])
-          os.replace(tmp, _LIB)
-    L = ctypes.CDLL(_LIB)
+    L = host_build.load(_SRC, 'ray_emu')
     vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     L.ray_emu_cast.argtypes = [ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cd, vp, vp, vp]
     L.ray_emu_cast.restype = None

@@ -13,7 +13,6 @@ import ctypes
 import glob
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -33,20 +32,13 @@ FIELDS = ('qpos', 'qvel', 'qacc', 'qacc_warmstart', 'sensordata', 'xpos', 'xquat
 def emus(tmp_path_factory):
   """tests/emu_lib.py twice, each on its own build of tests/emu/content_dims.cpp: (facts as computed, everything present)."""
   out = []
-  d = tmp_path_factory.mktemp('content_dims')
-  procs = []
+  d = str(tmp_path_factory.mktemp('content_dims'))
   for tag, flags in (('dims', []), ('nodims', ['-DDMC_NO_CONTENT_DIMS'])):
-    so = str(d / ('libemu_%s.so' % tag))
-    procs.append((tag, so, subprocess.Popen(
-        ['g++', '-O1', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas'] + flags +
-        ['-o', so, os.path.join(HERE, 'emu', 'content_dims.cpp')])))
-  for tag, so, p in procs:
-    assert p.wait() == 0, tag
     spec = importlib.util.spec_from_file_location('emu_lib_' + tag, os.path.join(HERE, 'emu_lib.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    mod._LIB = so      # (newer than every source: lib() loads it as it is and declares the entry points)
-    mod.lib().emu_content_dims.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L = mod.lib(os.path.join(HERE, 'emu', 'content_dims.cpp'), 'emu_' + tag, flags=flags, opt='-O1', out_dir=d)
+    L.emu_content_dims.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     out.append(mod)
   return out
 

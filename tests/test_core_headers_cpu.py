@@ -2,7 +2,6 @@
 the step kernels' sources (dm_control_amd/build.py STEP_SOURCES: build staleness, the key of the plugin cache, the host
 build of the tests)."""
 import os
-import re
 import subprocess
 
 import pytest
@@ -22,25 +21,10 @@ def test_header_is_self_contained(header, tmp_path):
   subprocess.check_call(['g++', '-std=c++17', '-fsyntax-only', '-DDMC_HOST_EMU', str(tu)])
 
 
-def _includes(path):
-  """Quoted includes of a file, resolved; generated headers and macro-named includes are not sources."""
-  out = []
-  with open(path) as f:
-    for line in f:
-      m = re.match(r'\s*#\s*include\s+"([^"]+)"', line)
-      if m and not m.group(1).endswith('.gen.h'):
-        out.append(os.path.normpath(os.path.join(os.path.dirname(path), m.group(1))))
-  return out
-
-
 def _reach(roots):
-  seen, todo = set(), [os.path.join(build.CSRC, r) for r in roots]
-  while todo:
-    p = todo.pop()
-    if p not in seen:
-      seen.add(p)
-      todo.extend(_includes(p))
-  return seen - {os.path.join(build.CSRC, r) for r in roots}
+  """What the roots include, followed through (build._own_includes); generated headers are not sources."""
+  roots = [os.path.join(build.CSRC, r) for r in roots]
+  return {p for r in roots for p in build._own_includes(r) if not p.endswith('.gen.h')} - set(roots)      # pylint: disable=protected-access
 
 
 def test_source_list_is_complete():
@@ -63,3 +47,12 @@ def test_consumers_derive_from_the_list():
   assert set(units['dmc_api.hip'][2]) == set(build.STEP_SOURCES) | {'camera_core.h'}
   for h in HEADERS + ('step_core.h',):
     assert h in build.STEP_SOURCES
+
+
+def test_own_includes_follow_the_headers_headers():
+  """ray_kernels.hip reaches camera_core.h through ray_core.h alone: the staleness checks of the library build and of the
+  tests' host builds (tests/host_build.py) see a header however deep it is included."""
+  src = os.path.join(build.CSRC, 'ray_kernels.hip')
+  with open(src) as f:
+    assert '"camera_core.h"' not in f.read()
+  assert os.path.join(build.CSRC, 'camera_core.h') in build._own_includes(src)      # pylint: disable=protected-access

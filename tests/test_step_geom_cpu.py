@@ -10,10 +10,11 @@ them and the distances within 1e-9 max(1, t), the bound DESIGN.md records for th
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANE, SPHERE, CAPSULE, ELLIPSOID, CYLINDER, BOX = 0, 2, 3, 4, 5, 6      # include/dmc_model_layout.h DMC_GEOM_*
@@ -23,10 +24,7 @@ NRAYS = 200
 
 @pytest.fixture(scope='module')
 def rays(tmp_path_factory):
-  so = str(tmp_path_factory.mktemp('geom_emu') / 'libgeom_emu.so')
-  subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unknown-pragmas', '-o', so,
-                         os.path.join(ROOT, 'tests', 'emu', 'geom_emu.cpp')])
-  lib = ctypes.CDLL(so)
+  lib = host_build.load(os.path.join(ROOT, 'tests', 'emu', 'geom_emu.cpp'), 'geom_emu', out_dir=str(tmp_path_factory.mktemp('geom_emu')))
   lib.geom_emu_rays.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 8
   lib.geom_emu_rays.restype = None
 
