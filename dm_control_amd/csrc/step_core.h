@@ -33,6 +33,10 @@ namespace dmc {
 #ifdef DMC_HOST_EMU
 inline int& emu_split_solves() { static int n = 0; return n; }
 inline long long* emu_ls_counts() { static long long n[6] = {0, 0, 0, 0, 0, 0}; return n; }      // line searches, their cost evaluations, noslip passes, their sweeps, QCQP calls, their iterations      // solves whose H was taken as block diagonal over the trees (tests)
+// line-search PASSES (a fused pass of primal_search's bracket phase -- ls_eval_multi -- counts once, whatever it evaluates;
+// emu_ls_counts()[1] keeps counting the evaluations of the sequential algorithm), searches that entered the bracket
+// phase, fused passes
+inline long long* emu_ls_passes() { static long long n[3] = {0, 0, 0}; return n; }
 #endif
 
 #if defined(DMC_PROFILE) && !defined(DMC_HOST_EMU)
@@ -3255,12 +3259,82 @@ struct StepCore {
     p->d1 = 2*q2 + cd1;
     if (p->d1 <= 0) p->d1 = (T)DMC_MINVAL;
   }
+  // primal_search's bracket phase evaluates its independent candidates in ONE pass (ls_eval_multi below).
+  // -DDMC_NO_LS_FUSED: one evaluation after the other, the search as it was (tests/test_ls_fused_cpu.py,
+  // tests/test_gpu_ls_fused.py build against it).
+#if !defined(DMC_NO_LS_FUSED)
+  static constexpr bool kLsFused = true;
+#else
+  static constexpr bool kLsFused = false;
+#endif
+#if !defined(DMC_HOST_EMU)
+  // The register branch of ls_eval with its contraction SPELT OUT: fp32 is compiled with contraction on, and the fused pass
+  // is another shape of the same text -- which product of `a*a*q2 + a*q1 + q0` ends up in the FMA is the compiler's choice
+  // per function body (see nr_dot).  Contraction off in these bodies and the FMAs as fmaf, as every call site of ls_eval's
+  // register branch compiled in the library's fp32 kernels (scripts/isa_by_source.py; the vectoriser pairs cost and
+  // slope into packed instructions there): the activity test x = fma(a, jv, jar); the lane's terms one product each,
+  // added to a zero; cost = fma(a, q1, (a*a)*q2) + q0; d0 = (2a)*q2 + q1 with the product ROUNDED (it shares a v_pk_mul
+  // with nothing to fuse into).  fp64 is built without contraction: the same expressions, every product rounded.
+  DMC_DEV static T ls_fma(T a, T b, T c) {
+#pragma clang fp contract(off)
+    if constexpr (sizeof(T) == 4) return __builtin_fmaf(a, b, c);
+    else return a*b + c;      // (the fp64 units are built without contraction)
+  }
+  DMC_DEV static void ls_terms_regs(T a, const LSRows& rw, T* q0, T* q1, T* q2) {
+#pragma clang fp contract(off)
+    // (selects instead of ls_eval's branches -- the same values, everything is in registers -- so that the candidates of
+    // a pass are one basic block the scheduler can interleave)
+    const T jar = rw.jar, jv = rw.jv, D = rw.D, dj0 = D*jar, zero = 0;
+    const T x = ls_fma(a, jv, jar);
+    const bool act_a = x < 0, act_0 = jar < 0, sw = act_a != act_0;
+    const T h2 = zero + (T)0.5*D*jv*jv, h1 = jv*dj0;
+    if (ls_relative<T>()) {
+      const T h0 = zero + (act_a ? (T)0.5 : (T)-0.5)*jar*dj0;
+      *q0 = sw ? h0 : zero;
+      if (ls_anchored<T>()) { const T s1 = zero + (act_a ? h1 : -h1); *q1 = sw ? s1 : zero; }
+      else { const T s1 = zero + h1; *q1 = act_a ? s1 : zero; }
+      *q2 = act_a ? h2 : zero;
+    } else {
+      const T h0 = zero + (T)0.5*jar*dj0, s1 = zero + h1;
+      *q0 = act_a ? h0 : zero; *q1 = act_a ? s1 : zero; *q2 = act_a ? h2 : zero;
+    }
+  }
+  // (s0, s1, s2: the group's sums of the lanes' terms)
+  DMC_DEV static void ls_point_regs(LSPoint* p, T a, T s0, T s1, T s2, const T* qg) {
+#pragma clang fp contract(off)
+    const T q0 = s0 + (ls_relative<T>() ? (T)0 : qg[0]), q1 = s1 + qg[1], q2 = s2 + qg[2];
+    p->cost = ls_fma(a, q1, a*a*q2) + q0;
+    p->d0 = 2*a*q2 + q1;
+    p->d1 = 2*q2;
+    if (p->d1 <= 0) p->d1 = (T)DMC_MINVAL;
+  }
+  // K independent points in one pass: the lane's terms for each, the 3 K reductions side by side, the points
+  template <int K, int RED>
+  DMC_DEV static void ls_points_regs(const T (&al)[K], LSPoint (&r)[K], const T* qg, const LSRows& rw) {
+    T s[3*K];
+#pragma unroll
+    for (int k = 0; k < K; k++) ls_terms_regs(al[k], rw, &s[k], &s[K + k], &s[2*K + k]);
+    group_sum_n<RED, 3*K>(s);
+#pragma unroll
+    for (int k = 0; k < K; k++) { r[k].alpha = al[k]; ls_point_regs(&r[k], al[k], s[k], s[K + k], s[2*K + k], qg); }
+  }
+#endif
   template <int RED = LPE>      // (RED: lanes of the reductions over register-resident rows -- kRegsRed from primal_search<true>)
   DMC_DEV void ls_eval(LSPoint* p, const T* qg, int nefc, int* evals, const LSRows& rw) {
 #ifdef DMC_HOST_EMU
-    emu_ls_counts()[1]++;
+    emu_ls_counts()[1]++; emu_ls_passes()[0]++;
 #endif
     if (general_rows()) { if (rw.gen) ls_eval_gen(p, qg, rw); else ls_eval_ell(p, qg, nefc); (*evals)++; return; }
+#if !defined(DMC_HOST_EMU)
+    if (kLsFused && rw.on) {
+      const T al[1] = {p->alpha};
+      LSPoint r[1];
+      ls_points_regs<1, RED>(al, r, qg, rw);
+      *p = r[0];
+      (*evals)++;
+      return;
+    }
+#endif
     if (rw.on) {
       const T a = p->alpha, jar = rw.jar, jv = rw.jv;
       T q0 = 0, q1 = 0, q2 = 0;
@@ -3297,6 +3371,66 @@ struct StepCore {
     }
     if (flag) { pnext->alpha = p->alpha - p->d0/p->d1; ls_eval<RED>(pnext, qg, nefc, evals, rw); }
     return flag;
+  }
+  // ls_update_bracket's decision alone: which candidate replaces *p.  It needs no evaluation -- the successor's alpha
+  // follows from the new *p, and primal_search evaluates it together with the trip's other independent points.
+  // (Written with selects: as nested branches the three candidates were ~100 instructions each, most of them exec-mask
+  // bookkeeping, on the path of the wave the launch waits for.  The two conditions exclude each other.)
+  DMC_DEV static int ls_pick_bracket(LSPoint* p, const LSPoint* cand) {
+    int flag = 0;
+    LSPoint q = *p;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const LSPoint c = cand[i];
+      const bool lo = (q.d0 < 0) & (c.d0 < 0) & (q.d0 < c.d0), hi = (q.d0 > 0) & (c.d0 > 0) & (q.d0 > c.d0), take = lo | hi;
+      flag = lo ? 1 : (hi ? 2 : flag);
+      q.alpha = take ? c.alpha : q.alpha; q.cost = take ? c.cost : q.cost; q.d0 = take ? c.d0 : q.d0; q.d1 = take ? c.d1 : q.d1;
+    }
+    *p = q;
+    return flag;
+  }
+  // Up to three INDEPENDENT line-search points in one pass: those of pa, pb, pc whose flag is set (their alphas are the
+  // caller's; the others are left alone and not counted).  Register-resident one-sided rows: the lane forms its row's terms
+  // for every candidate and the three reductions of each are issued side by side -- independent DPP chains fill each
+  // other's latency (scripts/instr_cost_probe.hip: 5-6 cycles per instruction of four independent chains, 8-9 of one
+  // dependent chain).  Per candidate the arithmetic is ls_eval's, expression for expression (ls_points_regs).
+  // Every other row kind: ls_eval per point, in the sequential search's order.
+  template <int RED = LPE>
+  DMC_DEV void ls_eval_multi(LSPoint* pa, LSPoint* pb, LSPoint* pc, bool ea, bool eb, bool ec, const T* qg, int nefc, int* evals, const LSRows& rw) {
+#if !defined(DMC_HOST_EMU)
+    if (!general_rows() && rw.on) {
+      // (an instruction costs the wave its issue slot even when nothing waits for it -- DESIGN.md section 4 -- so a pass
+      // evaluates exactly the points that are on: three, two or one.  The points move by value: a selected POINTER would
+      // pin the caller's points in scratch memory.)
+      const int n = (ea ? 1 : 0) + (eb ? 1 : 0) + (ec ? 1 : 0);
+      *evals += n;
+      if (n == 3) {
+        T al[3] = {pa->alpha, pb->alpha, pc->alpha};
+        LSPoint r[3];
+        ls_points_regs<3, RED>(al, r, qg, rw);
+        *pa = r[0]; *pb = r[1]; *pc = r[2];
+      } else if (n == 2) {      // x: the first point that is on, y: the last
+        T al[2] = {ea ? pa->alpha : pb->alpha, ec ? pc->alpha : pb->alpha};
+        LSPoint r[2];
+        ls_points_regs<2, RED>(al, r, qg, rw);
+        if (ea) *pa = r[0]; else *pb = r[0];
+        if (ec) *pc = r[1]; else *pb = r[1];
+      } else if (n == 1) {
+        T al[1] = {ea ? pa->alpha : (eb ? pb->alpha : pc->alpha)};
+        LSPoint r[1];
+        ls_points_regs<1, RED>(al, r, qg, rw);
+        if (ea) *pa = r[0]; else if (eb) *pb = r[0]; else *pc = r[0];
+      }
+      return;
+    }
+#endif
+    if (ea) ls_eval<RED>(pa, qg, nefc, evals, rw);
+    if (eb) ls_eval<RED>(pb, qg, nefc, evals, rw);
+    if (ec) ls_eval<RED>(pc, qg, nefc, evals, rw);
+#ifdef DMC_HOST_EMU
+    const int n = (ea ? 1 : 0) + (eb ? 1 : 0) + (ec ? 1 : 0);
+    if (n > 1) { emu_ls_passes()[0] -= n - 1; emu_ls_passes()[2]++; }      // (ls_eval counted a pass each)
+#endif
   }
   // REGS (primal_solve_regs): M v and J v are the caller's, in registers -- `pre` brings the lane's terms of the four dof
   // sums and its row's (jar, jv, D); everything from the reductions on is this routine's, unchanged.
@@ -3374,6 +3508,42 @@ struct StepCore {
     if (evals >= lsmax) { *lscost = p1.cost; return p1.alpha; }
     if (!p2update) { *lscost = p1.cost; return p1.alpha; }
     p2next = p1;
+#ifdef DMC_HOST_EMU
+    emu_ls_passes()[1]++;
+#endif
+    // The bracket phase on fused passes.  The sequential search (below, -DDMC_NO_LS_FUSED) runs p1next, then per trip pmid,
+    // the successor of each bracket end that moved, and so on: five dependent evaluations in a typical search of a late
+    // Newton iteration, where the data need two.  p1next and the first pmid depend on p1 and p2 alone; and once a trip's
+    // candidates are known, both bracket updates are decided without an evaluation (ls_pick_bracket), which gives the
+    // alphas of both successors AND of the next trip's pmid.  So: one pass on entry, one per trip (ls_eval_multi).
+    // The same points are evaluated with the same arithmetic and the same decisions are taken on them, so the result is
+    // the sequential search's to the bit.  The cap keeps its meaning: pmid rides along only when the sequential search
+    // would have reached it, evals + (successors) + 1 <= lsmax -- otherwise the pass evaluates and counts the
+    // successors alone (the sequential search evaluates them without asking the cap) and the loop ends as its
+    // `while (evals < lsmax)` would; nothing is evaluated speculatively.
+    if constexpr (kLsFused) {
+      bool e1 = true, e2 = false;      // entry: p1next is p1's successor, p2next is p1 itself
+      p1next.alpha = p1.alpha - p1.d0/p1.d1;
+      for (;;) {
+        const bool mid = evals + (e1 ? 1 : 0) + (e2 ? 1 : 0) < lsmax;
+        pmid.alpha = (T)0.5*(p1.alpha + p2.alpha);
+        ls_eval_multi<RED>(&p1next, &p2next, &pmid, e1, e2, mid, qg, nefc, &evals, rw);
+        if (!mid) break;
+        LSPoint cand[3] = {p1next, p2next, pmid};
+        bool found = false; T best_cost = 0, best_alpha = 0;   // first candidate of lowest cost (selects, as ls_pick_bracket)
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+          const bool ok = (t_abs(cand[i].d0) < gtol) & (!found | (cand[i].cost < best_cost));
+          best_cost = ok ? cand[i].cost : best_cost; best_alpha = ok ? cand[i].alpha : best_alpha; found |= ok;
+        }
+        if (found) { *lscost = best_cost; return best_alpha; }
+        const int b1 = ls_pick_bracket(&p1, cand), b2 = ls_pick_bracket(&p2, cand);
+        if (!b1 && !b2) { if (pmid.cost < p0.cost) { *lscost = pmid.cost; return pmid.alpha; } return 0; }
+        e1 = b1 != 0; e2 = b2 != 0;
+        if (e1) p1next.alpha = p1.alpha - p1.d0/p1.d1;
+        if (e2) p2next.alpha = p2.alpha - p2.d0/p2.d1;
+      }
+    } else {
     p1next.alpha = p1.alpha - p1.d0/p1.d1; ls_eval<RED>(&p1next, qg, nefc, &evals, rw);
     while (evals < lsmax) {
       pmid.alpha = (T)0.5*(p1.alpha + p2.alpha); ls_eval<RED>(&pmid, qg, nefc, &evals, rw);
@@ -3386,6 +3556,7 @@ struct StepCore {
       const int b1 = ls_update_bracket<RED>(&p1, cand, &p1next, qg, nefc, &evals, rw);
       const int b2 = ls_update_bracket<RED>(&p2, cand, &p2next, qg, nefc, &evals, rw);
       if (!b1 && !b2) { if (pmid.cost < p0.cost) { *lscost = pmid.cost; return pmid.alpha; } return 0; }
+    }
     }
     if (p1.cost <= p2.cost && p1.cost < p0.cost) { *lscost = p1.cost; return p1.alpha; }
     if (p2.cost <= p1.cost && p2.cost < p0.cost) { *lscost = p2.cost; return p2.alpha; }

@@ -50,6 +50,23 @@ template <int LPE, typename V> DMC_DEV V group_sum(V v) {
 #endif
   return v;
 }
+// N independent group sums, step by step side by side: each is group_sum's pairing tree (the same bits), and a step of
+// one chain fills the wait of the others' DPP moves (a dependent chain pays the full latency at every step).
+// Each step's result passes through an empty asm: left alone, the SLP vectoriser pairs the chains' adds into v_pk_add_f32,
+// and a packed add cannot take the DPP move as its operand -- a step of a pair was then two zeroing moves, two
+// v_mov_b32_dpp and the packed add, five instructions where two v_add_f32_dpp do it.
+template <int LPE, int N, typename V> DMC_DEV void group_sum_n(V (&v)[N]) {
+#ifndef DMC_HOST_EMU
+#define DMC_EACH(expr) _Pragma("unroll") for (int k = 0; k < N; k++) { expr; asm("" : "+v"(v[k])); }
+  if (LPE >= 2) DMC_EACH(v[k] += dpp_f<0xB1>(v[k]))
+  if (LPE >= 4) DMC_EACH(v[k] += dpp_f<0x4E>(v[k]))
+  if (LPE >= 8) DMC_EACH(v[k] += dpp_f<0x141>(v[k]))
+  if (LPE >= 16) DMC_EACH(v[k] += dpp_f<0x140>(v[k]))
+  if (LPE >= 32) DMC_EACH(v[k] = xsum<16>(v[k]))
+  if (LPE >= 64) DMC_EACH(v[k] = xsum<32>(v[k]))
+#undef DMC_EACH
+#endif
+}
 // value held by lane `k` of each group when k is WAVE-uniform (a loop counter): v_readlane
 // into an SGPR (one per group of the wave) instead of a trip through the LDS crossbar
 #ifndef DMC_HOST_EMU
