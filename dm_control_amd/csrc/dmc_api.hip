@@ -348,7 +348,7 @@ static int batch_init(dmc_batch* b, int nconmax, int njmax, int lanes_per_env, i
   if (dev_alloc(b, &b->d_work, 32 * 9 * sizeof(int), true, "work queue")) return -2;
   // (a mocap pose is an input of mj_kinematics that the stash's (qpos, qvel) comparison does not see: no stash for those models)
   if (!getenv("DMC_NO_KSTASH") && !d.nmocap) {
-    const size_t nk = (size_t)d.nq + d.nv + (L.s_qM - L.s_xpos);
+    const size_t nk = (size_t)kstash_record(d.nq, d.nv, L.s_qM - L.s_xpos, L.s_xpos, (int)b->elem).stride;      // (step_layout.h)
     if (dev_alloc(b, &b->d_kstash, (size_t)b->B * nk * b->elem, false, "kinematic stash") ||
         dev_alloc(b, &b->d_kstash_i, (size_t)b->B * sizeof(int), true, "kinematic stash")) return -2;      // epoch 0: never valid
   }
@@ -516,6 +516,7 @@ static int launch(dmc_batch* b, int nstep, int legacy, LaunchMode mode, void* st
   return rc;
 }
 
+static int bump_epoch(dmc_batch* b, hipStream_t stream, bool wait);
 extern "C" int dmc_batch_attach_specialised(dmc_batch* b, const char* so_path) {
   if (!b || !so_path) return fail("null argument");
   void* h = dlopen(so_path, RTLD_NOW | RTLD_LOCAL);
@@ -541,7 +542,9 @@ extern "C" int dmc_batch_attach_specialised(dmc_batch* b, const char* so_path) {
   tb_t tb = (tb_t)dlsym(h, "dmc_spec_task_args_bytes");
   b->spec_task_bytes = tb ? tb() : 0;
   b->task_on = 0;
-  return 0;
+  // the record of the kinematic stash is the kernel's choice (StepCore::krec: packed in a -DDMC_NO_WIDE_IO build): what
+  // the kernel that ran so far left behind is not for the one that runs from here on
+  return bump_epoch(b, 0, true);
 }
 
 extern "C" int dmc_batch_set_task_args(dmc_batch* b, const void* args, int nbytes) {

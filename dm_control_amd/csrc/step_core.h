@@ -129,7 +129,7 @@ struct StepIO {
   // recorded into a HIP graph is replayed with it -- a by-value epoch would be frozen at capture time.
   T* stash_r; int* stash_i; const int* epoch;
   // kinematic stash (on by default): what mj_kinematics / mj_comPos / mj_comVel derive from (qpos, qvel), kept per env
-  // between legacy steps; (nq + nv + n_kin, ...) reals env-major and one epoch int per env (StepCore::load_kstash)
+  // between legacy steps; one record of reals per env (kstash_record, step_layout.h) and one epoch int per env (StepCore::load_kstash)
   T* kstash; int* kstash_i;
   long long* prof;   // optional (DMC_PROFILE builds): (PROF_N, B) cycle counters
   T* debug;      // optional: (n_sr, ndebug) dump of the env scratch after forward
@@ -404,16 +404,33 @@ struct StepCore {
   // global memory together with the (qpos, qvel) they belong to; the next launch takes them back iff its state is
   // bit-equal (and no model constant was edited: the epoch), so writes to bound tensors need no notification.
   DMC_DEV int kin_count() const { return L.s_qM - L.s_xpos; }
+  // -DDMC_NO_WIDE_IO (and the host build): the launch's entry and exit as they were -- the packed stash record moved real
+  // by real, the time stored with the state, every pointer and datum of the exit fetched from LDS where it is used
+#if defined(DMC_NO_WIDE_IO) || defined(DMC_HOST_EMU)
+  static constexpr bool kWideIO = false;
+#else
+  static constexpr bool kWideIO = true;
+  // a 16-byte piece of reals.  An environment's scratch starts on a 16-byte boundary of LDS (every table and scratch
+  // count of step_layout_build is a multiple of four elements) and its stash record on one of global memory
+  // (kstash_record: the stride is whole pieces), so piece j of the record's range and of the scratch's are both aligned.
+  typedef T TV __attribute__((ext_vector_type(16 / sizeof(T))));
+#endif
+  static constexpr int kE = 16 / (int)sizeof(T);      // reals of a piece
+  DMC_DEV static KStashRecord krec(const StepLayout& L) {
+    const int head = L.d.nq + L.d.nv, nk = L.s_qM - L.s_xpos;
+    return kWideIO ? kstash_record(L.d.nq, L.d.nv, nk, L.s_xpos, (int)sizeof(T)) : KStashRecord{head, head + nk};
+  }
   DMC_DEV bool load_kstash(const StepIO<T>& io, int env) {
     env = late(env);
     if (io.kstash_i[env] != get_epoch()) return false;
     const int nq = L.d.nq, nv = L.d.nv, nk = kin_count();
-    const T* h = io.kstash + (size_t)env*(nq + nv + nk);
+    const KStashRecord kr = krec(L);
+    const T* h = io.kstash + (size_t)env*kr.stride;
     int bad = 0;
     FOR_LANES(i, nq) if (!(h[i] == S(qpos)[i])) bad = 1;
     FOR_LANES(i, nv) if (!(h[nq + i] == S(qvel)[i])) bad = 1;
     if (group_max<LPE>(bad)) return false;
-    FOR_LANES(i, nk) S(xpos)[i] = h[nq + nv + i];
+    FOR_LANES(i, nk) S(xpos)[i] = h[kr.kin + i];
     DMC_WSYNC();
     kstash_env_geoms();
     return true;
@@ -421,10 +438,39 @@ struct StepCore {
   DMC_DEV void store_kstash(const StepIO<T>& io, int env) {
     env = late(env);
     const int nq = L.d.nq, nv = L.d.nv, nk = kin_count();
-    DMC_GLB T* h = G(io.kstash) + (size_t)env*(nq + nv + nk);
+    const KStashRecord kr = krec(L);
+    DMC_GLB T* h = G(io.kstash) + (size_t)env*kr.stride;
+#if !defined(DMC_NO_WIDE_IO) && !defined(DMC_HOST_EMU)
+    {
+      // the range's whole pieces as ds_read_b128 -> global_store_dwordx4 (a model-specialised kernel: straight-line, every
+      // read before the first wait); what the first and the last piece hold of the range goes real by real, so that
+      // nothing next to the range -- in the record: the tail of qvel -- is written
+      const int pad = kr.kin % kE, a = pad ? (kE - pad < nk ? kE - pad : nk) : 0, nf = (nk - a) / kE, b = a + nf*kE;
+      const TV* sv = reinterpret_cast<const TV*>(S(xpos) + a);
+      DMC_GLB TV* hv = reinterpret_cast<DMC_GLB TV*>(h + kr.kin + a);
+      if constexpr (LS::kNKin > 0) {
+        constexpr int trips = (LS::kNKin / kE + LPE - 1) / LPE;      // (nf <= kNKin / kE)
+        TV v[trips];
+        if (nf > 0) {      // (a trip past the last piece reads the last one once more and drops it on its registers)
+#pragma unroll
+          for (int k = 0; k < trips; k++) { const int j = lane + k*LPE; v[k] = sv[j < nf ? j : nf - 1]; }
+#pragma unroll
+          for (int k = 0; k < trips; k++) { const int j = lane + k*LPE; if (j < nf) hv[j] = v[k]; }
+        }
+      } else {
+        for (int j = lane; j < nf; j += LPE) hv[j] = sv[j];
+      }
+      FOR_LANES(i, nq) h[i] = S(qpos)[i];
+      FOR_LANES(i, nv) h[nq + i] = S(qvel)[i];
+      FOR_LANES(i, a) h[kr.kin + i] = S(xpos)[i];
+      for (int i = b + lane; i < nk; i += LPE) h[kr.kin + i] = S(xpos)[i];
+      if (lane == 0) G(io.kstash_i)[env] = get_epoch();
+      return;
+    }
+#endif
     FOR_LANES(i, nq) h[i] = S(qpos)[i];
     FOR_LANES(i, nv) h[nq + i] = S(qvel)[i];
-    FOR_LANES(i, nk) h[nq + nv + i] = S(xpos)[i];
+    FOR_LANES(i, nk) h[kr.kin + i] = S(xpos)[i];
     if (lane == 0) G(io.kstash_i)[env] = get_epoch();
   }
   // ---- launch-entry loads ------------------------------------------------------------------------------------------
@@ -447,11 +493,19 @@ struct StepCore {
   // register budget (the hand-off code cost the queued 9-dof kernel 460 B of scratch per lane) and their items are short
   static constexpr bool kSlices = LS::kNV <= 0 || LS::kNV > 16;
   static constexpr int kPFKin = LS::kNKin > 0 ? ((LS::kNKin + LPE - 1) / LPE < 24 ? (LS::kNKin + LPE - 1) / LPE : 24) : 0;
+  // ... as 16-byte pieces (kWideIO): the pieces that hold the range, at most kNKin / kE + 2 of them, the first and the
+  // last possibly shared with what lies next to the range
+  static constexpr int kNCh = LS::kNKin > 0 ? (LS::kNKin + 2*kE - 2) / kE : 0;
+  static constexpr int kPFCh = kNCh ? ((kNCh + LPE - 1) / LPE < 24 / kE ? (kNCh + LPE - 1) / LPE : 24 / kE) : 0;
   struct Entry { int em, fast, kvalid, epoch; };
   struct EntryRegs {
     T qpos, qvel, warm, qfrc, ctrl, act, kq, kv;
     int ktag, epoch;
+#if defined(DMC_NO_WIDE_IO) || defined(DMC_HOST_EMU)
     T kd[kPFKin ? kPFKin : 1];
+#else
+    TV kc[kPFCh ? kPFCh : 1];
+#endif
   };
   DMC_DEV static bool kstash_applies(const StepOpts<T>& o, const StepIO<T>& io, int mode, int legacy) {
     return io.kstash && mode == 0 && legacy && o.integrator != DMC_INT_RK4 && !io.stash_r;
@@ -479,11 +533,20 @@ struct StepCore {
     if (!kstash_applies(o, io, mode, legacy)) return;
     r->ktag = G(io.kstash_i)[env]; r->epoch = e->epoch;
     const int nk = L.s_qM - L.s_xpos;
-    const DMC_GLB T* h = G(io.kstash) + (size_t)env*(nq + nv + nk);
+    const KStashRecord kr = krec(L);
+    const DMC_GLB T* h = G(io.kstash) + (size_t)env*kr.stride;
     r->kq = lane < nq ? h[lane] : (T)0;
     r->kv = lane < nv ? h[nq + lane] : (T)0;
+#if defined(DMC_NO_WIDE_IO) || defined(DMC_HOST_EMU)
 #pragma unroll
-    for (int k = 0; k < kPFKin; k++) { const int i = lane + k*LPE; r->kd[k] = i < nk ? h[nq + nv + i] : (T)0; }
+    for (int k = 0; k < kPFKin; k++) { const int i = lane + k*LPE; r->kd[k] = i < nk ? h[kr.kin + i] : (T)0; }
+#else
+    // piece j of the range: reals [j kE - pad, (j + 1) kE - pad) of it; past the last one the last once more, dropped in entry_commit
+    const int pad = kr.kin % kE, nch = (pad + nk + kE - 1) / kE;
+    const DMC_GLB TV* hv = reinterpret_cast<const DMC_GLB TV*>(h + (kr.kin - pad));
+#pragma unroll
+    for (int k = 0; k < kPFCh; k++) { const int j = lane + k*LPE; r->kc[k] = hv[j < nch ? j : nch - 1]; }
+#endif
   }
   // s: the LDS scratch of the env (of this lane's group)
   DMC_DEV static void entry_commit(const StepLayout& L, const StepIO<T>& io, int env, int lane, Entry* e, const EntryRegs& r, T* s) {
@@ -497,12 +560,33 @@ struct StepCore {
     const int bad = ((lane < nq && !(r.kq == r.qpos)) || (lane < nv && !(r.kv == r.qvel))) ? 1 : 0;
     if (group_max<LPE>(bad)) return;
     const int nk = L.s_qM - L.s_xpos;
+    const KStashRecord kr = krec(L);
+#if defined(DMC_NO_WIDE_IO) || defined(DMC_HOST_EMU)
 #pragma unroll
     for (int k = 0; k < kPFKin; k++) { const int i = lane + k*LPE; if (i < nk) s[L.s_xpos + i] = r.kd[k]; }
     if (kPFKin*LPE < nk) {
-      const T* h = io.kstash + (size_t)env*(nq + nv + nk) + nq + nv;
+      const T* h = io.kstash + (size_t)env*kr.stride + kr.kin;
       for (int i = lane + kPFKin*LPE; i < nk; i += LPE) s[L.s_xpos + i] = h[i];
     }
+#else
+    // a piece wholly inside the range is one ds_write_b128; the first and the last write only their reals of the range
+    const int pad = kr.kin % kE, nch = (pad + nk + kE - 1) / kE;
+    TV* sv = reinterpret_cast<TV*>(s + (L.s_xpos - pad));
+#pragma unroll
+    for (int k = 0; k < kPFCh; k++) {
+      const int j = lane + k*LPE, lo = j*kE - pad;
+      if (j >= nch) continue;
+      if (lo >= 0 && lo + kE <= nk) sv[j] = r.kc[k];
+      else {
+#pragma unroll
+        for (int c = 0; c < kE; c++) if (lo + c >= 0 && lo + c < nk) s[L.s_xpos + lo + c] = r.kc[k][c];
+      }
+    }
+    if (kPFCh*LPE < nch) {      // (what the prefetch registers do not hold: in place)
+      const T* h = io.kstash + (size_t)env*kr.stride + kr.kin;
+      for (int i = (kPFCh ? kPFCh*LPE*kE - pad : 0) + lane; i < nk; i += LPE) s[L.s_xpos + i] = h[i];
+    }
+#endif
     e->kvalid = 1;
   }
   // per-environment geoms are inputs the stash does not compare: their world poses are taken from the rows again
@@ -555,16 +639,45 @@ struct StepCore {
     FOR_LANES(i, L.d.nsensordata) S(sensordata)[i] = 0;
     DMC_WSYNC();
   }
-  DMC_DEV void store_state(const StepIO<T>& io, int env) {
+  // The time goes out FIRST of everything a launch stores: its value comes from memory (this object lives across the
+  // out-of-line stages), and a wait for that load behind the ~n_kin stores of the kinematic stash waits for every one
+  // of them to be acknowledged -- vmcnt counts loads and stores alike.
+  DMC_DEV void store_time(const StepIO<T>& io, int env) {
+    env = late(env);
+    if (lane == 0) G(io.time)[env] = time_;
+  }
+  DMC_DEV void store_state(const StepIO<T>& io, int env, bool time_stored = false) {
     env = late(env);
     const int B = io.B;
+#if !defined(DMC_NO_WIDE_IO) && !defined(DMC_HOST_EMU)
+    const int nq = L.d.nq, nv = L.d.nv, na = L.d.na;
+    if (nq <= LPE && nv <= LPE && na <= LPE && L.d.nu <= LPE) {
+      // one element per lane: every pointer in one group of LDS reads, every datum in the next, then the stores
+      DMC_GLB T* const p_qpos = G(io.qpos); DMC_GLB T* const p_qvel = G(io.qvel); DMC_GLB T* const p_warm = G(io.qacc_warmstart);
+      DMC_GLB T* const p_act = G(io.act); DMC_GLB double* const p_time = G(io.time);
+      int* const p_warn = io.warning; T* const p_ctrl = io.ctrl;
+      const T v_qpos = lane < nq ? S(qpos)[lane] : (T)0, v_qvel = lane < nv ? S(qvel)[lane] : (T)0;
+      const T v_warm = lane < nv ? S(qacc_warmstart)[lane] : (T)0, v_act = (na && lane < na) ? S(act)[lane] : (T)0;
+      const int v_warn = (LPE >= 16 && lane < DMC_NWARNING) ? SI(imisc)[IM_WARN + lane] : 0;
+      const int badctrl = SI(imisc)[IM_WARN + DMC_WARN_BADCTRL];
+      if (!time_stored && lane == 0) p_time[env] = time_;
+      if (lane < nq) p_qpos[(size_t)lane*B + env] = v_qpos;
+      if (lane < nv) { p_qvel[(size_t)lane*B + env] = v_qvel; p_warm[(size_t)lane*B + env] = v_warm; }
+      if (na && lane < na) p_act[(size_t)lane*B + env] = v_act;
+      // (atomics: see below)
+      if (LPE >= 16) { if (lane < DMC_NWARNING && v_warn) atomicAdd(p_warn + (size_t)lane*B + env, v_warn); }
+      else if (lane == 0) for (int k = 0; k < DMC_NWARNING; k++) if (SI(imisc)[IM_WARN + k]) atomicAdd(p_warn + (size_t)k*B + env, SI(imisc)[IM_WARN + k]);
+      if (badctrl && lane < L.d.nu) p_ctrl[(size_t)lane*B + env] = S(ctrl)[lane];      // (rare: the one read behind the batch)
+      return;
+    }
+#endif
     FOR_LANES(i, L.d.nq) G(io.qpos)[(size_t)i*B + env] = S(qpos)[i];
     FOR_LANES(i, L.d.nv) {
       G(io.qvel)[(size_t)i*B + env] = S(qvel)[i];
       G(io.qacc_warmstart)[(size_t)i*B + env] = S(qacc_warmstart)[i];
     }
     if (L.d.na) FOR_LANES(i, L.d.na) G(io.act)[(size_t)i*B + env] = S(act)[i];
-    if (lane == 0) G(io.time)[env] = time_;
+    if (!time_stored && lane == 0) G(io.time)[env] = time_;
     // (one lane per warning counter: lane 0 walking the nine of them was nine dependent LDS round trips at the end of every wave)
     // (atomics: an earlier piece of a sliced item may have added its own from another CU, which this CU's L1 would not show)
 #ifndef DMC_HOST_EMU
@@ -5330,13 +5443,14 @@ struct StepCore {
     if (!stepping) dump_debug(io, env);
     // an environment the launch override turned into mj_forward (just re-initialised) reports its one state in every slot
     if (!stepping && launch_mode == 0) probe_store(io, env, 0, nstep);
+    if (kWideIO) store_time(io, env);
     if (!stepping || legacy || mode == 3) { DMC_PROF(PROF_TRAIL); store_outputs(io, env, outmask); }
     // the stash holds a complete position / velocity stage at the CURRENT state only after a legacy step (after an
     // mj_forward the Cholesky buffer holds the factor of H, not of M; a non-legacy mj_step ends before mj_step1)
     if (stash) store_stash(io, env, mode == 0 && legacy && !fwd_after);      // (after the forward the Cholesky buffer holds H's factor)
     // the trailing stage (partial or full) evaluated kinematics / COM frame / velocities at the state being stored
     if (io.kstash && mode == 0 && legacy && o.integrator != DMC_INT_RK4) store_kstash(io, env);
-    store_state(io, env);
+    store_state(io, env, kWideIO);
     DMC_PROF(PROF_STORE);
     prof_end(io, env);
   }

@@ -53,10 +53,23 @@ struct LaunchGeom {
 template <typename T> constexpr int stepopts_lds_bytes() { return (int)((sizeof(StepOpts<T>) + 15) / 16 * 16); }
 template <typename T> constexpr int opts_lds_bytes() { return stepopts_lds_bytes<T>() + (int)((sizeof(StepIO<T>) + 15) / 16 * 16); }
 
+#ifndef DMC_NO_WIDE_IO
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#define DMC_KARG __attribute__((address_space(4)))
+// Where the by-value StepIO sits in the kernel-argument segment of step_kernel / step_kernel_static: the explicit
+// arguments lie in declaration order from byte 0, each at its natural alignment.  karg0: the offset of StepOpts (what
+// precedes it: the generic kernel's layout pointer); three table pointers stand between the two structs.
+template <typename T> constexpr int kernarg_io_offset(int karg0) {
+  static_assert(alignof(StepOpts<T>) == 8 && alignof(StepIO<T>) == 8 && sizeof(StepOpts<T>) % 8 == 0 && sizeof(StepIO<T>) % 8 == 0, "kernel-argument layout");
+  return karg0 + (int)sizeof(StepOpts<T>) + 3 * (int)sizeof(void*);
+}
+#endif
+
 // QUEUE = false: every wave has exactly one item (the batch fits the resident grid) -- no claim loop, so nothing of
 // the body is "loop invariant": with the loop the kernel arguments are hoisted out of it, spilled to VGPR lanes
 // (106 SGPRs hold a fraction of StepIO's ~60 pointers) and read back with v_readlane where they are used.
-template <typename T, int LPE, typename LS, bool QUEUE>
+// KARG0: byte offset of the StepOpts argument in the calling kernel's argument segment
+template <typename T, int LPE, typename LS, bool QUEUE, int KARG0>
 __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg, const int* __restrict__ g_mi,
                                                  const T* __restrict__ g_mr, const int* __restrict__ g_mc, const StepIO<T>& io_arg, int nstep, int legacy,
                                                  int mode, int outmask, int nsub) {
@@ -90,11 +103,34 @@ __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg
   // dispatch), so that everything an environment leaves in global memory between its pieces is written and read
   // through ONE L2.  (The per-XCD L2s are not coherent with each other: two of them holding dirty lines of the same
   // per-env scratch could write them back in either order.)  A position is claimed with one atomicAdd on the queue's head.
-  // the argument structs go to LDS first (read from there by everything behind the barrier): with the queue's claim -- an
-  // atomic round trip -- in front of these copies the compiler parked both structs in every lane's scratch (+ 500 B)
-  if (tid == 0) *o_lds = o_arg;
+  // The argument structs go to LDS (read from there by everything behind the barrier).  -DDMC_NO_WIDE_IO: copied out of
+  // SGPRs by one lane each, and first -- with the queue's claim, an atomic round trip, in front of these copies the
+  // compiler parked both structs in every lane's scratch (+ 500 B).
   StepIO<T>* io_lds = reinterpret_cast<StepIO<T>*>(smem + stepopts_lds_bytes<T>());
+#ifdef DMC_NO_WIDE_IO
+  if (tid == 0) *o_lds = o_arg;
   if (tid == 64 % nthr) *io_lds = io_arg;
+#else
+  // ... cooperatively: thread i carries dword i of (StepOpts, StepIO) from the kernel-argument segment to LDS, as vector
+  // loads that travel with the table loads below (one lane moving a struct out of SGPRs was ~140 instructions that every
+  // wave of the workgroup waited for at the barrier).  Requested here, written behind the claim with everything else.
+  constexpr int n_argo = (int)(sizeof(StepOpts<T>) / 4), n_arg = n_argo + (int)(sizeof(StepIO<T>) / 4);
+  constexpr int arg_trips = (n_arg + 63) / 64;      // (a workgroup has at least one wave)
+  constexpr int io_off = kernarg_io_offset<T>(KARG0);
+  unsigned areg[arg_trips];
+  {
+    const DMC_KARG unsigned char* ka = (const DMC_KARG unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll
+    for (int k = 0; k < arg_trips; k++) {
+      areg[k] = 0;
+      if (k * nthr < n_arg) {      // (uniform)
+        int d = tid + k * nthr;
+        d = d < n_arg ? d : n_arg - 1;      // out of range: a valid dword, dropped below
+        areg[k] = *(const DMC_KARG unsigned*)(ka + (d < n_argo ? KARG0 + 4 * d : io_off + 4 * (d - n_argo)));
+      }
+    }
+  }
+#endif
   const StepIO<T>& io = *io_lds;
   int* const q_work = QUEUE ? io_arg.work : nullptr;
   int* const q_prog = QUEUE ? io_arg.prog : nullptr;
@@ -128,12 +164,56 @@ __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg
     en.em = io_arg.env_mode ? io_arg.env_mode[e0] : 0; en.fast = 0; en.kvalid = 0; en.epoch = *io_arg.epoch;
   }
   // stage the model constant tables once per workgroup (shared by all its envs)
-  for (int i = tid; i < L.n_mi; i += nthr) mi[i] = g_mi[i];
-  for (int i = tid; i < L.n_mr_lds; i += nthr) mr[i] = g_mr[i];   // large models: only the hot tables (StepLayout::n_mr_lds)
   // small models: the cold tables ride along in LDS (after the real tables); large ones read them from global memory
   int* mc_lds = reinterpret_cast<int*>(tables + (size_t)L.n_mi * sizeof(int) + (size_t)L.n_mr_lds * sizeof(T));
   const size_t cold_bytes = L.d.coldlds ? (size_t)L.n_mc * sizeof(int) : 0;
+#ifdef DMC_NO_WIDE_IO
+  for (int i = tid; i < L.n_mi; i += nthr) mi[i] = g_mi[i];
+  for (int i = tid; i < L.n_mr_lds; i += nthr) mr[i] = g_mr[i];   // large models: only the hot tables (StepLayout::n_mr_lds)
   if (L.d.coldlds) for (int i = tid; i < L.n_mc; i += nthr) mc_lds[i] = g_mc[i];
+#else
+  // The three tables lie back to back in LDS and every count is a multiple of four elements (step_layout_build), so the
+  // workgroup copies ONE list of 16-byte chunks (large models: only the hot real tables, StepLayout::n_mr_lds): up to
+  // kTableBatch chunks per thread are requested before anything is waited for -- a model-specialised kernel knows the
+  // counts, and the trips its workgroup does not need fall to a uniform test -- and only then written.  (A loop of
+  // load -> wait -> write per table was six dependent global round trips for the 9-dof model's 256 threads.)
+  {
+    constexpr int kTableBatch = 4;
+    const int c_mi = L.n_mi / 4, c_mr = c_mi + (int)((size_t)L.n_mr_lds * sizeof(T) / 16);
+    const int c_all = c_mr + (L.d.coldlds ? L.n_mc / 4 : 0);
+    // (chunk c of the list is at src(c) + 16 c: a select between three uniform addresses, not three branches)
+    const unsigned long long a_mi = (unsigned long long)g_mi, a_mr = (unsigned long long)g_mr - 16ull * (unsigned)c_mi,
+                             a_mc = (unsigned long long)g_mc - 16ull * (unsigned)c_mr;
+    u32x4* dst = reinterpret_cast<u32x4*>(tables);
+    __builtin_assume(nthr >= 64);      // (whole waves: a model whose list fits the first batch of one wave has no loop)
+    auto batch = [&](int base) {
+      u32x4 treg[kTableBatch];
+#pragma unroll
+      for (int k = 0; k < kTableBatch; k++) {
+        if (base + k * nthr < c_all) {      // (uniform; a trip that is skipped here writes nothing below)
+          int c = base + k * nthr + tid;
+          c = c < c_all ? c : c_all - 1;      // out of range: the last chunk once more, dropped below
+          const unsigned long long a = c < c_mi ? a_mi : (c < c_mr ? a_mr : a_mc);
+          treg[k] = *(const DMC_GLB u32x4*)(a + 16ull * (unsigned)c);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kTableBatch; k++) {
+        const int c = base + k * nthr + tid;
+        if (c < c_all) dst[c] = treg[k];
+      }
+    };
+    // the first batch stands outside the loop: its loads follow the state's and the stash's without a wait in between
+    batch(0);
+#pragma clang loop vectorize(disable) unroll(disable)
+    for (int base = kTableBatch * nthr; base < c_all; base += kTableBatch * nthr) batch(base);
+#pragma unroll
+    for (int k = 0; k < arg_trips; k++) {      // (the oldest loads of the launch: nothing left to wait for)
+      const int d = tid + k * nthr;
+      if (d < n_arg) *reinterpret_cast<unsigned*>(smem + (d < n_argo ? 4 * d : stepopts_lds_bytes<T>() + 4 * (d - n_argo))) = areg[k];
+    }
+  }
+#endif
   if (have_item && piece == 0) Core::entry_commit(L, io_arg, env0, tid % LPE, &en, er, reinterpret_cast<T*>(tables + tables_bytes + (size_t)(tid / LPE) * env_bytes));
   __syncthreads();
   // An item is the 64 / LPE environments one wave steps together.  Without a queue every wave has the item of its
@@ -229,7 +309,7 @@ step_kernel(const StepLayout* __restrict__ Lp, StepOpts<T> o, const int* __restr
   // generic kernel: the layout lives in device memory (uniform scalar loads); taking
   // the address of a by-value kernel argument would copy it to scratch
   DynLayoutSrc ls; ls.p = Lp;
-  step_kernel_body<T, LPE, DynLayoutSrc, QUEUE>(ls, o, g_mi, g_mr, g_mc, io, nstep, legacy, mode, outmask, nsub);
+  step_kernel_body<T, LPE, DynLayoutSrc, QUEUE, (int)sizeof(const StepLayout*)>(ls, o, g_mi, g_mr, g_mc, io, nstep, legacy, mode, outmask, nsub);
 }
 
 #if DMC_NSTATIC > 0
@@ -252,7 +332,7 @@ template <typename T, int LPE, int SID, bool QUEUE>
 __global__ void __launch_bounds__(DMC_MAX_THREADS, DMC_MIN_WAVES)
 step_kernel_static(StepOpts<T> o, const int* __restrict__ g_mi, const T* __restrict__ g_mr,
                    const int* __restrict__ g_mc, StepIO<T> io, int nstep, int legacy, int mode, int outmask, int nsub) {
-  step_kernel_body<T, LPE, StaticLayout<SID>, QUEUE>(StaticLayout<SID>(), o, g_mi, g_mr, g_mc, io, nstep, legacy, mode, outmask, nsub);
+  step_kernel_body<T, LPE, StaticLayout<SID>, QUEUE, 0>(StaticLayout<SID>(), o, g_mi, g_mr, g_mc, io, nstep, legacy, mode, outmask, nsub);
 }
 #endif
 

@@ -292,6 +292,20 @@ struct StepLayout {
   int gs_xquat, gs_geom_xmat, gs_cinert, gs_cdof_dot;      // level 3: the kinematic arrays that left LDS
 };
 
+// The record of the kinematic stash (StepIO::kstash), one per environment, in reals of `elem` bytes:
+// [qpos (nq) | qvel (nv) | gap | kinematic range (nk = s_qM - s_xpos)].  The gap (fewer reals than a 16-byte piece holds)
+// gives the range the phase its LDS copy has against a 16-byte boundary, and the stride is a whole number of such
+// pieces: a piece of the record and the piece of the scratch it mirrors are both aligned, so the range travels in
+// 16-byte accesses between its (partial) first and last piece.  One definition for the kernels (StepCore::load_kstash,
+// store_kstash, entry_issue) and for the allocation (dmc_api.hip); the host build and -DDMC_NO_WIDE_IO kernels keep the
+// packed record (range at nq + nv, stride nq + nv + nk), which fits the same allocation.
+struct KStashRecord { int kin, stride; };      // offset of the range, reals from one record to the next
+constexpr KStashRecord kstash_record(int nq, int nv, int nk, int s_xpos, int elem) {
+  const int e = 16 / elem, head = nq + nv;
+  const int kin = head + ((s_xpos - head) % e + e) % e;
+  return KStashRecord{kin, (kin + nk + e - 1) / e * e};
+}
+
 // scalar options broadcast to every wave
 template <typename T>
 struct StepOpts {
