@@ -371,12 +371,15 @@ template <typename T> DMC_DEV int sphere_cylinder_core(Hit<T>* hit, T margin, co
   const T a[3] = {m2[2], m2[5], m2[8]}, R = s2[0], H = s2[1];
   T closest[3], n[3], dist;
   const T g = point_cylinder(ps, p2, a, R, H, closest);
-  if (g >= (T)DMC_MINVAL) {
+  const T v[3] = {ps[0] - p2[0], ps[1] - p2[1], ps[2] - p2[2]};
+  const T x = dot3(v, a), perp[3] = {v[0] - x*a[0], v[1] - x*a[1], v[2] - x*a[2]}, d = t_sqrt(dot3(perp, perp));
+  // the centre inside the solid is told from its coordinates: g is then the rounding noise of p + x a + perp - q, in
+  // fp32 some 1e-8 and far above DMC_MINVAL (a normal made of noise, dist = -rs)
+  const bool inside = t_abs(x) <= H && d <= R;
+  if (!inside && g >= (T)DMC_MINVAL) {
     dist = g - rs;
     for (int k = 0; k < 3; k++) n[k] = (closest[k] - ps[k]) / g;
   } else {      // centre inside the solid: out through the nearest face
-    const T v[3] = {ps[0] - p2[0], ps[1] - p2[1], ps[2] - p2[2]};
-    const T x = dot3(v, a), perp[3] = {v[0] - x*a[0], v[1] - x*a[1], v[2] - x*a[2]}, d = t_sqrt(dot3(perp, perp));
     if (H - t_abs(x) < R - d) { dist = -(H - t_abs(x)) - rs; for (int k = 0; k < 3; k++) n[k] = x >= 0 ? -a[k] : a[k]; }
     else {
       dist = -(R - d) - rs;

@@ -65,7 +65,7 @@ struct StepTables {
   std::vector<int> mc;       // cold int tables (global memory), per L.mc_*
   std::vector<double> mr;    // real tables (fp64 master copy), per L.mr_*
   StepOpts<double> opts;
-  int max_contacts, max_rows;  // upper bounds if no cap applied
+  int max_contacts, max_rows;  // upper bounds if no cap applied (one contact per capsule-capsule pair: the default caps' sums)
   int has_unsupported_pairs = 0;  // pair types outside the collision kernel (legal only with contacts disabled)
 };
 
@@ -192,6 +192,7 @@ inline bool step_tables_build(StepTables* t, const HostModel& m, int nconmax, in
   d.ntri = m.nv * (m.nv + 1) / 2;
   // contact / row caps
   int maxc = 0, maxr = 0, nlim = 0;
+  int capc = 0, capr = 0;      // the same sums with both contacts of every capsule-capsule pair (see below)
   for (int j = 0; j < m.njnt; j++) if (m.jnt_limited[j]) nlim++;
   std::vector<int> pdim(m.npair);
   for (int p = 0; p < m.npair; p++) {
@@ -216,7 +217,7 @@ inline bool step_tables_build(StepTables* t, const HostModel& m, int nconmax, in
     if (t1 == DMC_GEOM_PLANE && t2 == DMC_GEOM_CAPSULE) nc = 2;
     else if (t1 == DMC_GEOM_PLANE && t2 == DMC_GEOM_BOX) nc = 4;
     if (plane_cyl) nc = 4;
-    else if (t1 == DMC_GEOM_CAPSULE && t2 == DMC_GEOM_CAPSULE) nc = 1;   // 2 only for exactly parallel axes
+    else if (t1 == DMC_GEOM_CAPSULE && t2 == DMC_GEOM_CAPSULE) nc = 1;   // 2 only for exactly parallel axes: counted in capc
     const bool known = (t1 == DMC_GEOM_PLANE && (t2 == DMC_GEOM_SPHERE || t2 == DMC_GEOM_CAPSULE || t2 == DMC_GEOM_BOX)) ||
                        (t1 == DMC_GEOM_SPHERE && (t2 == DMC_GEOM_SPHERE || t2 == DMC_GEOM_CAPSULE)) ||
                        (t1 == DMC_GEOM_CAPSULE && t2 == DMC_GEOM_CAPSULE) || ell || boxp;
@@ -231,7 +232,12 @@ inline bool step_tables_build(StepTables* t, const HostModel& m, int nconmax, in
     else dim = m.geom_condim[pr1 > pr2 ? g1 : g2];
     pdim[p] = dim;
     if (cyl && !cylx) nc = 0;
-    maxc += nc; maxr += nc * (dim == 1 ? 1 : (elliptic ? dim : 2*(dim - 1)));
+    const int prow = dim == 1 ? 1 : (elliptic ? dim : 2*(dim - 1));
+    // two capsules proper with parallel axes touch in two places (mjc_CapsuleCapsule): the default caps count one contact
+    // for the pair, a caller who asks for more than those sums is held to the sums with two
+    const int ncap = (nc == 1 && m.geom_type[g1] == DMC_GEOM_CAPSULE && m.geom_type[g2] == DMC_GEOM_CAPSULE) ? 2 : nc;
+    maxc += nc; maxr += nc * prow;
+    capc += ncap; capr += ncap * prow;
   }
   // contact parameters (mixing rules: max / priority / solmix).  Most pairs of a
   // model share one parameter tuple (all geoms at their defaults), so the tuples are stored once and the
@@ -269,9 +275,13 @@ inline bool step_tables_build(StepTables* t, const HostModel& m, int nconmax, in
   int maxrow_per_contact = 1;
   for (int p = 0; p < m.npair; p++) maxrow_per_contact = std::max(maxrow_per_contact, pdim[p] == 1 ? 1 : (elliptic ? pdim[p] : 2*(pdim[p] - 1)));
   if (nconmax <= 0) nconmax = std::min(maxc, 16);
-  nconmax = std::max(1, std::min(nconmax, std::max(1, maxc)));
+  // caps within the one-contact-per-capsule-pair sums (every default, every baked layout) are clipped as ever; only a
+  // caller's nconmax beyond them reaches the sums that hold the second contact of parallel capsules, and its rows
+  const bool wide = nconmax > maxc;
+  const int boundc = wide ? capc : maxc, boundr = wide ? capr : maxr;
+  nconmax = std::max(1, std::min(nconmax, std::max(1, boundc)));
   if (njmax <= 0) njmax = d.neqrow + d.nfric + nlim + d.nlimten + nconmax * maxrow_per_contact;
-  njmax = std::max(1, std::min(njmax, std::max(1, maxr + nlim + d.nlimten + d.nfric + d.neqrow)));
+  njmax = std::max(1, std::min(njmax, std::max(1, boundr + nlim + d.nlimten + d.nfric + d.neqrow)));
   d.nconmax = nconmax; d.njmax = njmax;
   d.elliptic = (elliptic && maxrow_per_contact > 1) ? 1 : 0;
   if (m.opt_noslip_iterations > 0) {
