@@ -30,6 +30,9 @@ IK_EXPORTS = ['dmc_ik_last_error', 'dmc_ik_create', 'dmc_ik_solve', 'dmc_ik_info
 # include/dmc_ray.h (batched ray casts: csrc/ray_kernels.hip)
 RAY_EXPORTS = ['dmc_rays_create', 'dmc_rays_cast', 'dmc_rays_add_scan', 'dmc_rays_scan', 'dmc_rays_info', 'dmc_rays_destroy']
 
+# include/dmc_dist.h (batched geom distances: csrc/dist_kernels.hip)
+DIST_EXPORTS = ['dmc_dist_create', 'dmc_dist_query', 'dmc_dist_info', 'dmc_dist_destroy', 'dmc_geom_distance_host']
+
 _lib = None
 
 
@@ -132,6 +135,14 @@ def lib():
     L.dmc_rays_info.argtypes = [vp, vp]
     L.dmc_rays_destroy.argtypes = [vp]
     L.dmc_rays_destroy.restype = None
+  if hasattr(L, 'dmc_dist_create'):      # (absent from the older libraries A/B runs load as variants)
+    L.dmc_dist_create.argtypes = [vp, ci, vp, vp, ci, vp, vp, ctypes.POINTER(vp)]
+    L.dmc_dist_query.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.dmc_dist_info.argtypes = [vp, vp]
+    L.dmc_dist_destroy.argtypes = [vp]
+    L.dmc_dist_destroy.restype = None
+    L.dmc_geom_distance_host.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp, cd, cd, ci, vp, vp]
+    L.dmc_geom_distance_host.restype = cd
   _lib = L
   return L
 

@@ -26,6 +26,7 @@ class BatchedPhysics:
       raise TypeError('model must be a compiled mjcf_compiler.Model')
     L = _native.lib()
     self.model = model
+    self.model_real = {}      # the host's record of what set_model_real wrote: {name: values}
     self.batch_size = int(batch_size)
     self.precision = precision
     self.device_id = device_id
@@ -219,6 +220,7 @@ class BatchedPhysics:
     """Rewrites a model constant shared by the whole batch (see dmc_batch_set_model_real)."""
     a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
     _native.check(_native.lib().dmc_batch_set_model_real(self._ptr, name.encode(), a.ctypes.data, a.size))
+    self.model_real[name] = a.copy()      # the host's record of the live table (mujoco_api.mj_geomDistance reads geom_size here)
 
   # -- per-environment model deltas ---------------------------------------------------------
   def set_env_geoms(self, names):

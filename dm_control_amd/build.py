@@ -41,7 +41,11 @@ _UNITS = [
                                                '../../include/dmc_ik.h', '../../include/dmc_batch.h']),
     # batched ray casts (fp32 and fp64: arbitrary rays, scans in a moving frame); the closed forms are the camera's
     ('ray_kernels.hip', [], ['ray_core.h', 'camera_core.h', '../../include/dmc_model_layout.h']),
-    # (the ray entry points' headers, ray_core.h and dmc_ray.h, reach the staleness check through _own_includes)
+    # batched geom distances (fp32 and fp64: GJK + EPA per (environment, pair)); no contraction: the fp64 instantiation
+    # rounds like the host build of the same header (dmc_geom_distance_host, the tests' emulation)
+    ('dist_kernels.hip', ['-ffp-contract=off'], ['dist_core.h', '../../include/dmc_model_layout.h']),
+    # (the ray and distance entry points' headers -- ray_core.h, dmc_ray.h, dist_core.h, dmc_dist.h -- reach the
+    # staleness check through _own_includes)
     ('dmc_api.hip', [], list(STEP_SOURCES) + ['camera_core.h']),
 ]
 

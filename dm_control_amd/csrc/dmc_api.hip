@@ -1727,3 +1727,109 @@ extern "C" int dmc_rays_scan(dmc_rays* r, void* dist_out, int32_t* geomid_out, v
     return rays_launch_t<decltype(t)>(r, true, 0, nullptr, nullptr, -1, nullptr, 0, dist_out, geomid_out, normal_out, hip_stream);
   });
 }
+
+// ---- batched geom distances (dist_core.h, dist_kernels.hip; include/dmc_dist.h) -----------------------------------
+#include "../../include/dmc_dist.h"
+#include "dist_core.h"
+struct dmc_dist {
+  dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
+  int ngeom, npair, nmember, iterations;
+  double tolerance;
+  int *d_type, *d_adr, *d_member;
+  void* d_distmax;      // T (npair) in the batch precision
+};
+extern "C" int dmc_dist_create(dmc_batch* b, int npair, const int32_t* pair_adr, const int32_t* member, int nmember,
+                               const double* distmax, const dmc_dist_options* opt, dmc_dist** out) {
+  if (!b || !pair_adr || !member || !distmax || !opt || !out) return fail("null argument");
+  const HostModel& m = b->model->hm;
+  if (npair < 1 || nmember < 2) return fail("dist: no pairs");
+  if (!(opt->tolerance > 0) || !(opt->tolerance < 1)) return fail("dist: tolerance must lie in (0, 1)");
+  if (opt->iterations < 1 || opt->iterations > 10000) return fail("dist: iterations must lie in [1, 10000]");
+  for (int i = 0; i < nmember; i++) {
+    if (member[i] < 0 || member[i] >= m.ngeom) return fail("dist: a member geom id is out of range");
+    if (!dist_supported(m.geom_type[member[i]]))
+      return fail("dist: geom " + std::to_string(member[i]) + " is a mesh or a height field: no distance to those");
+  }
+  for (int p = 0; p < npair; p++) {
+    const int32_t* a = pair_adr + 4*p;
+    if (a[1] < 1 || a[3] < 1) return fail("dist: pair " + std::to_string(p) + " has a member without geoms");
+    if (a[0] < 0 || a[2] < 0 || (long long)a[0] + a[1] > nmember || (long long)a[2] + a[3] > nmember)
+      return fail("dist: the member table of pair " + std::to_string(p) + " leaves the member list");
+    if (distmax[p] != distmax[p]) return fail("dist: distmax is NaN");
+  }
+  std::vector<int> type(std::max(1, m.ngeom));
+  for (int g = 0; g < m.ngeom; g++) type[g] = m.geom_type[g];
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_dist* d = new dmc_dist();      // (zeroed)
+  d->b = b; d->ngeom = m.ngeom; d->npair = npair; d->nmember = nmember; d->iterations = opt->iterations; d->tolerance = opt->tolerance;
+  int rc = dev_alloc(d, &d->d_type, sizeof(int)*type.size(), false, "dist geom types", type.data());
+  rc = rc ? rc : dev_alloc(d, &d->d_adr, sizeof(int)*4*npair, false, "dist pair table", pair_adr);
+  rc = rc ? rc : dev_alloc(d, &d->d_member, sizeof(int)*nmember, false, "dist member list", member);
+  rc = rc ? rc : by_precision(b, [&](auto t) {
+    using T = decltype(t);
+    std::vector<T> dm(npair);
+    for (int p = 0; p < npair; p++) dm[p] = (T)distmax[p];      // (infinity stays infinity: an unreached pair reads inf)
+    return dev_alloc(d, &d->d_distmax, sizeof(T)*npair, false, "dist cutoffs", dm.data());
+  });
+  if (rc) { dmc_dist_destroy(d); return rc; }
+  *out = d;
+  return 0;
+}
+extern "C" void dmc_dist_destroy(dmc_dist* d) {
+  if (!d) return;
+  dev_free_all(d);
+  delete d;
+}
+extern "C" int dmc_dist_info(const dmc_dist* d, int* info) {
+  if (!d || !info) return fail("null argument");
+  const bool f64 = d->b->precision == 64;
+  const int V = f64 ? DistCaps<double>::V : DistCaps<float>::V, F = f64 ? DistCaps<double>::F : DistCaps<float>::F,
+            K = f64 ? DistCaps<double>::K : DistCaps<float>::K, es = f64 ? 8 : 4;
+  const int v[10] = {d->b->B, d->b->precision, d->npair, d->nmember, d->iterations, kDistBlock, V, F, K,
+                     es*((3*V + F)*K + kDistGeomReals*kDistBlock) + 4*F*K};
+  for (int k = 0; k < 10; k++) info[k] = v[k];
+  return 0;
+}
+extern "C" int dmc_dist_query(dmc_dist* d, void* dist_out, void* fromto_out, void* normal_out, int32_t* status_out, void* hip_stream) {
+  if (!d) return fail("null dist");
+  if (!dist_out && !fromto_out && !normal_out && !status_out) return fail("dist query: nothing asked for");
+  if (int rc = poses_fresh(d->b, OUT_GEOM, "dist")) return rc;
+  HIP_TRY(hipSetDevice(d->b->device));
+  return by_precision(d->b, [&](auto t) {
+    using T = decltype(t);
+    DistArgs<T> a;
+    fill_pose_args(d->b, &a);
+    a.geom_type = d->d_type; a.adr = d->d_adr; a.member = d->d_member; a.distmax = (const T*)d->d_distmax;
+    a.npair = d->npair; a.iterations = d->iterations; a.tolerance = (T)d->tolerance;
+    a.dist = (T*)dist_out; a.fromto = (T*)fromto_out; a.normal = (T*)normal_out; a.status = status_out;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_dist_f64(a, hip_stream);
+    else rc = launch_dist_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "dist: the launch grid does not fit" : "dist: launch failed", -2);
+    return 0;
+  });
+}
+// one pair on the host in fp64, from the same dist_core.h (no device, no batch)
+extern "C" double dmc_geom_distance_host(int type1, const double* size1, const double* pos1, const double* mat1, int type2,
+                                         const double* size2, const double* pos2, const double* mat2, double distmax,
+                                         double tolerance, int iterations, double* fromto, int32_t* status) {
+  if (status) *status = -1;
+  if (fromto) for (int k = 0; k < 6; k++) fromto[k] = 0;
+  if (!size1 || !pos1 || !mat1 || !size2 || !pos2 || !mat2) { fail("null argument"); return distmax; }
+  if (!dist_supported(type1) || !dist_supported(type2)) { fail("geom distance: a mesh or a height field has no distance"); return distmax; }
+  if (!(tolerance > 0) || iterations < 1) { fail("geom distance: tolerance and iterations must be positive"); return distmax; }
+  DistGeom<double> g1, g2;
+  g1.type = type1; g2.type = type2;
+  for (int k = 0; k < 3; k++) { g1.size[k] = size1[k]; g1.pos[k] = pos1[k]; g2.size[k] = size2[k]; g2.pos[k] = pos2[k]; }
+  for (int k = 0; k < 9; k++) { g1.mat[k] = mat1[k]; g2.mat[k] = mat2[k]; }
+  std::vector<double> vtx(3*DistCaps<double>::V), fdist(DistCaps<double>::F);
+  std::vector<int> fidx(DistCaps<double>::F);
+  DistEpaMem<double> mem;
+  mem.vtx = vtx.data(); mem.fdist = fdist.data(); mem.fidx = fidx.data(); mem.stride = 1;
+  DistResult<double> r;
+  dist_pair_host(g1, g2, distmax, tolerance, iterations, mem, &r);
+  if (fromto) { fromto[0] = r.from.x; fromto[1] = r.from.y; fromto[2] = r.from.z; fromto[3] = r.to.x; fromto[4] = r.to.y; fromto[5] = r.to.z; }
+  if (status) *status = r.status != 0;
+  return r.dist;
+}

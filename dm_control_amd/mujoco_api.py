@@ -1634,6 +1634,45 @@ def mj_ray(m, d, pnt, vec, geomgroup, flg_static, bodyexclude, geomid):
   return float(x)
 
 
+def mj_geomDistance(m, d, geom1, geom2, distmax, fromto):
+  """mujoco.mj_geomDistance: the signed distance between two geoms (ids), bounded by `distmax`: the Euclidean distance
+  when they are apart, minus the penetration depth when they overlap; `fromto` (6,) or None receives the point on geom1
+  and the point on geom2 that realise it (zeros when nothing is closer than distmax).  Plane-plane returns distmax; meshes
+  and height fields are refused.  Tolerance and iterations are mjOption's ccd defaults (1e-6, 50).  Reads the kinematics
+  as they stand, like mj_ray; the solver is the library's host build of the device code (dmc_geom_distance_host)."""
+  import ctypes      # pylint: disable=import-outside-toplevel
+  from dm_control_amd import _native      # pylint: disable=import-outside-toplevel
+  _check(m, d)
+  c = m._c
+  g1, g2 = int(geom1), int(geom2)
+  for g in (g1, g2):
+    if not 0 <= g < c.ngeom:
+      raise FatalError('mj_geomDistance: geom id %d out of range [0, %d)' % (g, c.ngeom))
+  if not d._outputs_valid:
+    d._ensure_forward()
+  get = lambda n, *shape: np.asarray(d._batch.get(n), dtype=np.float64).reshape(shape)
+  xpos, xmat = get('geom_xpos', c.ngeom, 3), get('geom_xmat', c.ngeom, 9)
+  # sizes in force, as the device unit reads them: the live table after set_model_real, an environment's own for set_env_geoms geoms
+  size = np.array(getattr(d._batch, 'model_real', {}).get('geom_size', c.geom_size), dtype=np.float64).reshape(c.ngeom, 3)
+  env_geoms = getattr(d._batch, 'env_geoms', None)
+  if env_geoms:
+    rows = np.asarray(d._batch.get('env_geom'), dtype=np.float64).reshape(-1)
+    for k, name in enumerate(env_geoms):
+      size[c.name2id(name, 'geom')] = rows[16*k + 12:16*k + 15]
+  arg = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+  s1, p1, m1, s2, p2, m2 = arg(size[g1]), arg(xpos[g1]), arg(xmat[g1]), arg(size[g2]), arg(xpos[g2]), arg(xmat[g2])
+  ft = np.zeros(6)
+  status = ctypes.c_int32(0)
+  dist = _native.lib().dmc_geom_distance_host(int(c.geom_type[g1]), s1.ctypes.data, p1.ctypes.data, m1.ctypes.data,
+                                              int(c.geom_type[g2]), s2.ctypes.data, p2.ctypes.data, m2.ctypes.data,
+                                              float(distmax), 1e-6, 50, ft.ctypes.data, ctypes.byref(status))
+  if status.value < 0:
+    raise FatalError('mj_geomDistance: ' + _native.lib().dmc_last_error().decode())
+  if fromto is not None:
+    np.asarray(fromto).reshape(-1)[:6] = ft
+  return float(dist)
+
+
 def mj_objectVelocity(m, d, objtype, objid, res, flg_local):
   """core.py:522: 6D velocity (angular, linear) of a body / xbody / geom / site in the world or the object's own frame."""
   _check(m, d)
