@@ -33,6 +33,9 @@ RAY_EXPORTS = ['dmc_rays_create', 'dmc_rays_cast', 'dmc_rays_add_scan', 'dmc_ray
 # include/dmc_dist.h (batched geom distances: csrc/dist_kernels.hip)
 DIST_EXPORTS = ['dmc_dist_create', 'dmc_dist_query', 'dmc_dist_info', 'dmc_dist_destroy', 'dmc_geom_distance_host']
 
+# include/dmc_jac.h (batched Jacobians: csrc/jac_kernels.hip)
+JAC_EXPORTS = ['dmc_jac_create', 'dmc_jac_jacobian', 'dmc_jac_velocity', 'dmc_jac_force', 'dmc_jac_info', 'dmc_jac_destroy']
+
 _lib = None
 
 
@@ -143,6 +146,15 @@ def lib():
     L.dmc_dist_destroy.restype = None
     L.dmc_geom_distance_host.argtypes = [ci, vp, vp, vp, ci, vp, vp, vp, cd, cd, ci, vp, vp]
     L.dmc_geom_distance_host.restype = cd
+  if hasattr(L, 'dmc_jac_create'):
+    i64 = ctypes.c_int64
+    L.dmc_jac_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    L.dmc_jac_jacobian.argtypes = [vp, vp, vp, vp, vp]
+    L.dmc_jac_velocity.argtypes = [vp, ci, vp, vp]
+    L.dmc_jac_force.argtypes = [vp, vp, i64, i64, vp, i64, i64, vp, vp]
+    L.dmc_jac_info.argtypes = [vp, vp]
+    L.dmc_jac_destroy.argtypes = [vp]
+    L.dmc_jac_destroy.restype = None
   _lib = L
   return L
 

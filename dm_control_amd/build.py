@@ -44,8 +44,11 @@ _UNITS = [
     # batched geom distances (fp32 and fp64: GJK + EPA per (environment, pair)); no contraction: the fp64 instantiation
     # rounds like the host build of the same header (dmc_geom_distance_host, the tests' emulation)
     ('dist_kernels.hip', ['-ffp-contract=off'], ['dist_core.h', '../../include/dmc_model_layout.h']),
-    # (the ray and distance entry points' headers -- ray_core.h, dmc_ray.h, dist_core.h, dmc_dist.h -- reach the
-    # staleness check through _own_includes)
+    # batched Jacobians (fp32 and fp64: mj_jac, J qvel, J' f per (environment, target)); no contraction: the fp64
+    # instantiation rounds like the host build of the same header (the tests' emulation)
+    ('jac_kernels.hip', ['-ffp-contract=off'], ['jac_core.h', 'step_defs.h', 'step_math.h', '../../include/dmc_model_layout.h']),
+    # (the ray, distance and Jacobian entry points' headers -- ray_core.h, dmc_ray.h, dist_core.h, dmc_dist.h, jac_core.h,
+    # dmc_jac.h -- reach the staleness check through _own_includes)
     ('dmc_api.hip', [], list(STEP_SOURCES) + ['camera_core.h']),
 ]
 

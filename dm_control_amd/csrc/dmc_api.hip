@@ -1833,3 +1833,155 @@ extern "C" double dmc_geom_distance_host(int type1, const double* size1, const d
   if (status) *status = r.status != 0;
   return r.dist;
 }
+
+// ---- batched Jacobians (jac_core.h, jac_kernels.hip; include/dmc_jac.h) --------------------------------------------
+#include "../../include/dmc_jac.h"
+#include "jac_core.h"
+struct dmc_jac {
+  dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
+  int ntarget, ncol, maxdof, epb;
+  int *d_head, *d_ints;
+  void* d_reals;      // T in the batch precision
+};
+extern "C" int dmc_jac_create(dmc_batch* b, const dmc_jac_tables* tb, dmc_jac** out) {
+  if (!b || !tb || !out || !tb->dims || !tb->ints || !tb->reals) return fail("null argument");
+  *out = nullptr;
+  const HostModel& m = b->model->hm;
+  const int T = tb->ntarget, C = tb->ncol;
+  if (T < 1 || T > 65535) return fail("jac: between 1 and 65535 targets are needed");
+  if (C < 1 || C > m.nv) return fail("jac: the number of columns must lie in [1, nv]");
+  // every index the kernels follow is checked here, once
+  static const int qw[4] = {7, 4, 1, 1}, dw[4] = {6, 3, 1, 1};
+  std::vector<int> head((size_t)T*kJacHead, 0);
+  long long io = 0, ro = 0;
+  int maxdof = 0;
+  for (int t = 0; t < T; t++) {
+    const std::string who = "jac: target " + std::to_string(t) + ": ";
+    const JacDims d = {tb->dims[3*t], tb->dims[3*t + 1], tb->dims[3*t + 2]};
+    if (d.nb < 1 || d.nb > m.nbody || d.nj < 0 || d.nd < 0 || d.nj > d.nd) return fail(who + "inconsistent chain sizes");
+    if (d.nd > kJacMaxDof) return fail(who + std::to_string(d.nd) + " chain dofs, at most " + std::to_string(kJacMaxDof));
+    if (io + jac_nints(d) > tb->nints || ro + jac_nreals(d) > tb->nreals) return fail(who + "the tables are shorter than their sizes say");
+    const int32_t* bj = tb->ints + io; const int32_t* bn = bj + d.nb; const int32_t* jt = bn + d.nb; const int32_t* jq = jt + d.nj;
+    const int32_t* jd = jq + d.nj; const int32_t* dof = jd + d.nj; const int32_t* col = dof + d.nd;
+    std::vector<int> seen(d.nj, 0), covered(d.nd, 0);
+    for (int k = 0; k < d.nb; k++) {
+      const int j0 = bj[k], jn = bn[k];
+      int nball = 0;
+      if (jn < 0 || (jn > 0 && (j0 < 0 || (long long)j0 + jn > d.nj))) return fail(who + "body joint range outside the chain");
+      for (int j = j0; j < j0 + jn; j++) {
+        seen[j]++;
+        if (jt[j] == DMC_JNT_FREE && jn != 1) return fail(who + "a free joint must be its body's only joint");
+        nball += jt[j] == DMC_JNT_BALL;
+      }
+      if (nball > 1) return fail(who + "a body with two ball joints is not supported");
+    }
+    for (int j = 0; j < d.nj; j++) {
+      const int ty = jt[j];
+      if (seen[j] != 1) return fail(who + "every chain joint must belong to exactly one chain body");
+      if (ty < 0 || ty > 3) return fail(who + "unknown joint type");
+      if (jq[j] < 0 || jq[j] + qw[ty] > m.nq) return fail(who + "qpos address outside the model");
+      if (jd[j] < 0 || jd[j] + dw[ty] > d.nd) return fail(who + "dof slot outside the chain");
+      for (int i = 0; i < dw[ty]; i++) covered[jd[j] + i]++;
+    }
+    for (int k = 0; k < d.nd; k++) {
+      if (covered[k] != 1) return fail(who + "every chain dof must belong to exactly one chain joint");
+      if (dof[k] < 0 || dof[k] >= m.nv) return fail(who + "dof id outside the model");
+      if (col[k] < -1 || col[k] >= C) return fail(who + "output column outside [0, C)");
+    }
+    for (long long k = ro; k < ro + jac_nreals(d); k++) if (!std::isfinite(tb->reals[k])) return fail(who + "a table entry is not finite");
+    int* h = &head[(size_t)t*kJacHead];
+    h[0] = d.nb; h[1] = d.nj; h[2] = d.nd; h[4] = (int)io; h[5] = (int)ro;
+    io += jac_nints(d); ro += jac_nreals(d);
+    if (io > 0x7fffffffLL || ro > 0x7fffffffLL) return fail("jac: the tables are too long");
+    maxdof = std::max(maxdof, d.nd);
+  }
+  if (io != tb->nints || ro != tb->nreals) return fail("jac: the tables are longer than their sizes say");
+  const int rb = b->precision == 64 ? 8 : 4;
+  const int epb = std::min(kJacBlock, kJacForceLds/rb/C);
+  if (epb < 1) return fail("jac: " + std::to_string(C) + " columns do not fit one workgroup's LDS");
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_jac* j = new dmc_jac();      // (zeroed)
+  j->b = b; j->ntarget = T; j->ncol = C; j->maxdof = maxdof; j->epb = epb;
+  int rc = dev_alloc(j, &j->d_head, sizeof(int)*head.size(), false, "jac head table", head.data());
+  rc = rc ? rc : dev_alloc(j, &j->d_ints, sizeof(int)*std::max<size_t>(1, (size_t)io), false, "jac int tables", io ? tb->ints : nullptr);
+  rc = rc ? rc : by_precision(b, [&](auto t) {
+    using R = decltype(t);
+    std::vector<R> r(tb->reals, tb->reals + ro);
+    return dev_alloc(j, &j->d_reals, sizeof(R)*r.size(), false, "jac real tables", r.data());
+  });
+  if (rc) { dmc_jac_destroy(j); return rc; }
+  *out = j;
+  return 0;
+}
+extern "C" void dmc_jac_destroy(dmc_jac* j) {
+  if (!j) return;
+  dev_free_all(j);
+  delete j;
+}
+extern "C" int dmc_jac_info(const dmc_jac* j, int* info) {
+  if (!j || !info) return fail("null argument");
+  const int rb = j->b->precision == 64 ? 8 : 4;
+  const int v[10] = {j->b->B, j->b->precision, j->ntarget, j->ncol, kJacBlock, 128/rb, jac_tile_bytes(rb), j->epb,
+                     kJacForceLds, j->maxdof};
+  for (int k = 0; k < 10; k++) info[k] = v[k];
+  return 0;
+}
+template <typename T>
+static void jac_fill(const dmc_jac* j, JacArgs<T>* a) {
+  *a = JacArgs<T>();
+  a->head = j->d_head; a->ints = j->d_ints; a->reals = (const T*)j->d_reals;
+  a->qpos = (const T*)j->b->fields[F_qpos].dev; a->qvel = (const T*)j->b->fields[F_qvel].dev;      // (every call: a field can be rebound)
+  a->B = j->b->B; a->ntarget = j->ntarget; a->ncol = j->ncol; a->epb = j->epb;
+}
+extern "C" int dmc_jac_jacobian(dmc_jac* j, const void* point, void* jacp_out, void* jacr_out, void* hip_stream) {
+  if (!j) return fail("null jac");
+  if (!jacp_out && !jacr_out) return fail("jac: nothing asked for");
+  HIP_TRY(hipSetDevice(j->b->device));
+  return by_precision(j->b, [&](auto t) {
+    using T = decltype(t);
+    JacArgs<T> a;
+    jac_fill(j, &a);
+    a.point = (const T*)point; a.jacp = (T*)jacp_out; a.jacr = (T*)jacr_out;
+    a.vec = j->ncol % (16/(int)sizeof(T)) == 0 && ((uintptr_t)jacp_out | (uintptr_t)jacr_out) % 16 == 0;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_jac_f64(a, hip_stream);
+    else rc = launch_jac_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "jac: the launch grid does not fit" : "jac: launch failed", -2);
+    return 0;
+  });
+}
+extern "C" int dmc_jac_velocity(dmc_jac* j, int local, void* vel_out, void* hip_stream) {
+  if (!j || !vel_out) return fail("null argument");
+  HIP_TRY(hipSetDevice(j->b->device));
+  return by_precision(j->b, [&](auto t) {
+    using T = decltype(t);
+    JacArgs<T> a;
+    jac_fill(j, &a);
+    a.vel = (T*)vel_out; a.local = local != 0;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_jac_vel_f64(a, hip_stream);
+    else rc = launch_jac_vel_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "jac: the launch grid does not fit" : "jac: launch failed", -2);
+    return 0;
+  });
+}
+extern "C" int dmc_jac_force(dmc_jac* j, const void* force, int64_t force_env_stride, int64_t force_target_stride, const void* torque,
+                             int64_t torque_env_stride, int64_t torque_target_stride, void* qfrc_out, void* hip_stream) {
+  if (!j || !qfrc_out) return fail("null argument");
+  if (force_env_stride < 0 || force_target_stride < 0 || torque_env_stride < 0 || torque_target_stride < 0) return fail("jac: negative stride");
+  HIP_TRY(hipSetDevice(j->b->device));
+  return by_precision(j->b, [&](auto t) {
+    using T = decltype(t);
+    JacArgs<T> a;
+    jac_fill(j, &a);
+    a.force = (const T*)force; a.f_se = force_env_stride; a.f_st = force_target_stride;
+    a.torque = (const T*)torque; a.t_se = torque_env_stride; a.t_st = torque_target_stride;
+    a.qfrc = (T*)qfrc_out;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_jac_force_f64(a, hip_stream);
+    else rc = launch_jac_force_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "jac: the launch grid does not fit" : "jac: launch failed", -2);
+    return 0;
+  });
+}

@@ -1464,6 +1464,44 @@ def mj_jacSite(m, d, jacp, jacr, site):
          int(m._c.site_bodyid[int(site)]))
 
 
+def mj_jacGeom(m, d, jacp, jacr, geom):
+  """The Jacobian of a geom's centre (geom_xpos)."""
+  mj_jac(m, d, jacp, jacr, np.asarray(d._batch.get('geom_xpos'), dtype=np.float64).reshape(-1, 3)[int(geom)],
+         int(m._c.geom_bodyid[int(geom)]))
+
+
+def mj_jacBodyCom(m, d, jacp, jacr, body):
+  """The Jacobian of a body's centre of mass (xipos)."""
+  mj_jac(m, d, jacp, jacr, np.asarray(d._batch.get('xipos'), dtype=np.float64).reshape(-1, 3)[int(body)], body)
+
+
+def mj_jacPointAxis(m, d, jacPoint, jacAxis, point, axis, body):
+  """The Jacobian of a world point and of a world axis that both move with `body`: `jacPoint` = mj_jac's jacp at the
+  point, column k of `jacAxis` = jacr[:, k] x axis (the rate at which dof k turns the axis); (3, nv) each or None."""
+  nv = m._c.nv
+  jp, jr = np.empty((3, nv)), np.empty((3, nv))
+  mj_jac(m, d, jp, jr, point, body)
+  if jacPoint is not None:
+    np.asarray(jacPoint).reshape(3, nv)[...] = jp
+  if jacAxis is not None:
+    np.asarray(jacAxis).reshape(3, nv)[...] = np.cross(jr.T, np.asarray(axis, dtype=np.float64).ravel()).T
+
+
+def mj_applyFT(m, d, force, torque, point, body, qfrc_target):
+  """mujoco.mj_applyFT: adds to `qfrc_target` (nv,), in place, the joint forces of a Cartesian `force` applied at the
+  world `point` of `body` and of a `torque` -- jacp' force + jacr' torque; either of force / torque may be None."""
+  nv = m._c.nv
+  jp, jr = np.empty((3, nv)), np.empty((3, nv))
+  mj_jac(m, d, jp, jr, point, body)
+  q = np.asarray(qfrc_target).reshape(-1)
+  if q.shape[0] != nv:
+    raise FatalError('mj_applyFT: qfrc_target must have nv = %d entries' % nv)
+  if force is not None:
+    q += jp.T @ np.asarray(force, dtype=np.float64).ravel()
+  if torque is not None:
+    q += jr.T @ np.asarray(torque, dtype=np.float64).ravel()
+
+
 def mj_integratePos(m, qpos, qvel, dt):
   """utils/inverse_kinematics.py:208: `qpos` advanced in place."""
   q = np.asarray(qpos)
