@@ -36,6 +36,10 @@ DIST_EXPORTS = ['dmc_dist_create', 'dmc_dist_query', 'dmc_dist_info', 'dmc_dist_
 # include/dmc_jac.h (batched Jacobians: csrc/jac_kernels.hip)
 JAC_EXPORTS = ['dmc_jac_create', 'dmc_jac_jacobian', 'dmc_jac_velocity', 'dmc_jac_force', 'dmc_jac_info', 'dmc_jac_destroy']
 
+# include/dmc_dyn.h (batched dynamics: csrc/dyn_kernels.hip)
+DYN_EXPORTS = ['dmc_dyn_create', 'dmc_dyn_mass_matrix', 'dmc_dyn_bias', 'dmc_dyn_inverse', 'dmc_dyn_mul', 'dmc_dyn_solve', 'dmc_dyn_info',
+               'dmc_dyn_destroy']
+
 _lib = None
 
 
@@ -155,6 +159,17 @@ def lib():
     L.dmc_jac_info.argtypes = [vp, vp]
     L.dmc_jac_destroy.argtypes = [vp]
     L.dmc_jac_destroy.restype = None
+  if hasattr(L, 'dmc_dyn_create'):
+    i64 = ctypes.c_int64
+    L.dmc_dyn_create.argtypes = [vp, vp, ci, ctypes.POINTER(vp)]
+    L.dmc_dyn_mass_matrix.argtypes = [vp, vp, vp]
+    L.dmc_dyn_bias.argtypes = [vp, vp, vp]
+    L.dmc_dyn_inverse.argtypes = [vp, vp, i64, vp, vp]
+    L.dmc_dyn_mul.argtypes = [vp, vp, ci, vp, vp]
+    L.dmc_dyn_solve.argtypes = [vp, vp, ci, vp, vp]
+    L.dmc_dyn_info.argtypes = [vp, vp]
+    L.dmc_dyn_destroy.argtypes = [vp]
+    L.dmc_dyn_destroy.restype = None
   _lib = L
   return L
 

@@ -1985,3 +1985,137 @@ extern "C" int dmc_jac_force(dmc_jac* j, const void* force, int64_t force_env_st
     return 0;
   });
 }
+
+// ---- batched dynamics (dyn_core.h, dyn_kernels.hip; include/dmc_dyn.h) ---------------------------------------------
+#include "../../include/dmc_dyn.h"
+#include "dyn_core.h"
+struct dmc_dyn {
+  dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
+  DynDims d;
+  int W;
+  int* d_ints;
+  void* d_reals;      // T in the batch precision
+};
+extern "C" int dmc_dyn_create(dmc_batch* b, const dmc_dyn_tables* tb, int lanes_per_env, dmc_dyn** out) {
+  if (!b || !tb || !out || !tb->ints || !tb->reals) return fail("null argument");
+  *out = nullptr;
+  const HostModel& m = b->model->hm;
+  const DynDims d = {tb->nb, tb->nj, tb->nv, tb->nq, tb->nlevel, tb->nsub};
+  const int W = lanes_per_env;
+  if (W != 16 && W != 32 && W != 64) return fail("dyn: lanes_per_env must be 16, 32 or 64");
+  if (d.nv < 1 || d.nv > kDynMaxDof) return fail("dyn: nv must lie in [1, " + std::to_string(kDynMaxDof) + "]");
+  if (d.nv != m.nv || d.nq != m.nq) return fail("dyn: nv and nq must be the model's");
+  if (d.nb < 2 || d.nb > m.nbody || d.nj < 1 || d.nj > d.nv || d.nlevel < 1 || d.nlevel >= d.nb || d.nsub < d.nb ||
+      (long long)d.nsub > (long long)d.nb*d.nb)
+    return fail("dyn: inconsistent table sizes");
+  if (tb->nints != dyn_nints(d) || tb->nreals != dyn_nreals(d)) return fail("dyn: the tables do not have the length their sizes say");
+  // every index the kernels follow is checked here, once
+  const DynTab<double> t = dyn_tab<double>(d, tb->ints, tb->reals);
+  static const int qw[4] = {7, 4, 1, 1}, dw[4] = {6, 3, 1, 1};
+  std::vector<int> jseen(d.nj, 0), dseen(d.nv, 0), level(d.nb, -1);
+  if (t.level_adr[0] != 0 || t.level_adr[d.nlevel] != d.nb - 1) return fail("dyn: the levels must cover every body below the world");
+  for (int l = 0; l < d.nlevel; l++) {
+    if (t.level_adr[l + 1] < t.level_adr[l]) return fail("dyn: level_adr must not decrease");
+    for (int k = t.level_adr[l]; k < t.level_adr[l + 1]; k++) {
+      const int body = t.level_body[k];
+      if (body < 1 || body >= d.nb || level[body] >= 0) return fail("dyn: every body below the world belongs to exactly one level");
+      level[body] = l;
+    }
+  }
+  if (t.body_parent[0] != 0 || t.body_jntnum[0] != 0 || t.sub_adr[0] != 0 || t.sub_adr[d.nb] != d.nsub) return fail("dyn: inconsistent world body or subtree lists");
+  for (int k = 0; k < d.nb; k++) {
+    const std::string who = "dyn: body " + std::to_string(k) + ": ";
+    const int p = t.body_parent[k], j0 = t.body_jntadr[k], jn = t.body_jntnum[k];
+    if (k > 0 && (p < 0 || p >= k || (p > 0 && level[p] >= level[k]))) return fail(who + "a parent precedes its children, on an earlier level");
+    if (t.body_root[k] < 0 || t.body_root[k] >= d.nb || t.body_lastdof[k] < -1 || t.body_lastdof[k] >= d.nv) return fail(who + "root or last dof out of range");
+    if (t.sub_adr[k + 1] < t.sub_adr[k] || t.sub_adr[k + 1] > d.nsub) return fail(who + "subtree list out of range");
+    for (int s = t.sub_adr[k]; s < t.sub_adr[k + 1]; s++) if (t.sub_body[s] < 0 || t.sub_body[s] >= d.nb) return fail(who + "subtree member out of range");
+    if (jn < 0 || (jn > 0 && (j0 < 0 || (long long)j0 + jn > d.nj))) return fail(who + "joint range outside the model");
+    int nball = 0;
+    for (int j = j0; j < j0 + jn; j++) {
+      jseen[j]++;
+      if (t.jnt_type[j] == DMC_JNT_FREE && jn != 1) return fail(who + "a free joint must be its body's only joint");
+      nball += t.jnt_type[j] == DMC_JNT_BALL;
+    }
+    if (nball > 1) return fail(who + "a body with two ball joints is not supported");
+  }
+  for (int j = 0; j < d.nj; j++) {
+    const int ty = t.jnt_type[j];
+    if (jseen[j] != 1) return fail("dyn: every joint must belong to exactly one body");
+    if (ty < 0 || ty > 3) return fail("dyn: unknown joint type");
+    if (t.jnt_qadr[j] < 0 || t.jnt_qadr[j] + qw[ty] > d.nq) return fail("dyn: qpos address outside the model");
+    if (t.jnt_dadr[j] < 0 || t.jnt_dadr[j] + dw[ty] > d.nv) return fail("dyn: dof address outside the model");
+    for (int i = 0; i < dw[ty]; i++) dseen[t.jnt_dadr[j] + i]++;
+  }
+  for (int k = 0; k < d.nv; k++) {
+    if (dseen[k] != 1) return fail("dyn: every dof must belong to exactly one joint");
+    if (t.dof_body[k] < 1 || t.dof_body[k] >= d.nb) return fail("dyn: dof body out of range");
+    if (t.dof_parent[k] < -1 || t.dof_parent[k] >= k || t.dof_pred[k] < -1 || t.dof_pred[k] >= k) return fail("dyn: a dof's parent and predecessor precede it");
+    if (t.dof_rot[k] != 0 && t.dof_rot[k] != 1) return fail("dyn: dof_rot is 0 or 1");
+  }
+  for (int k = 0; k < tb->nreals; k++) if (!std::isfinite(tb->reals[k])) return fail("dyn: a table entry is not finite");
+  const int rb = b->precision == 64 ? 8 : 4;
+  if (dyn_tier(d.nb, d.nv, 0, W, rb) < 0 || dyn_tier(d.nb, d.nv, 1, W, rb) < 0)
+    return fail("dyn: " + std::to_string(kDynBlock/W) + " environments of nv = " + std::to_string(d.nv) + ", " + std::to_string(d.nb) +
+                " bodies do not fit one workgroup's LDS at " + std::to_string(W) + " lanes per environment");
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_dyn* y = new dmc_dyn();      // (zeroed)
+  y->b = b; y->d = d; y->W = W;
+  int rc = dev_alloc(y, &y->d_ints, sizeof(int)*(size_t)tb->nints, false, "dyn int tables", tb->ints);
+  rc = rc ? rc : by_precision(b, [&](auto z) {
+    using R = decltype(z);
+    std::vector<R> r(tb->reals, tb->reals + tb->nreals);
+    return dev_alloc(y, &y->d_reals, sizeof(R)*r.size(), false, "dyn real tables", r.data());
+  });
+  if (rc) { dmc_dyn_destroy(y); return rc; }
+  *out = y;
+  return 0;
+}
+extern "C" void dmc_dyn_destroy(dmc_dyn* y) {
+  if (!y) return;
+  dev_free_all(y);
+  delete y;
+}
+extern "C" int dmc_dyn_info(const dmc_dyn* y, int* info) {
+  if (!y || !info) return fail("null argument");
+  const int rb = y->b->precision == 64 ? 8 : 4;
+  const int v[10] = {y->b->B, y->b->precision, y->d.nv, y->d.nb, y->W, kDynBlock/y->W, kDynTierBytes[dyn_tier(y->d.nb, y->d.nv, 0, y->W, rb)],
+                     kDynTierBytes[dyn_tier(y->d.nb, y->d.nv, 1, y->W, rb)], kDynChunk, y->d.nlevel};
+  for (int k = 0; k < 10; k++) info[k] = v[k];
+  return 0;
+}
+// kind 0: the crb launch in `mode`; kind 1: the rne launch
+static int dyn_launch(dmc_dyn* y, int kind, int mode, const void* in, int64_t in_se, int K, void* out, void* hip_stream) {
+  if (!y || !out) return fail("null argument");
+  HIP_TRY(hipSetDevice(y->b->device));
+  return by_precision(y->b, [&](auto z) {
+    using T = decltype(z);
+    DynArgs<T> a = DynArgs<T>();
+    a.d = y->d; a.ints = y->d_ints; a.reals = (const T*)y->d_reals;
+    a.qpos = (const T*)y->b->fields[F_qpos].dev; a.qvel = (const T*)y->b->fields[F_qvel].dev;      // (every call: a field can be rebound)
+    a.B = y->b->B; a.W = y->W; a.mode = mode; a.in = (const T*)in; a.in_se = in_se; a.K = K; a.out = (T*)out;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = kind ? launch_dyn_rne_f64(a, hip_stream) : launch_dyn_crb_f64(a, hip_stream);
+    else rc = kind ? launch_dyn_rne_f32(a, hip_stream) : launch_dyn_crb_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "dyn: the launch does not fit" : "dyn: launch failed", -2);
+    return 0;
+  });
+}
+extern "C" int dmc_dyn_mass_matrix(dmc_dyn* y, void* M_out, void* hip_stream) { return dyn_launch(y, 0, DYN_MASS, nullptr, 0, 0, M_out, hip_stream); }
+extern "C" int dmc_dyn_bias(dmc_dyn* y, void* bias_out, void* hip_stream) { return dyn_launch(y, 1, 0, nullptr, 0, 0, bias_out, hip_stream); }
+extern "C" int dmc_dyn_inverse(dmc_dyn* y, const void* qacc, int64_t qacc_env_stride, void* tau_out, void* hip_stream) {
+  if (!qacc) return fail("null argument");
+  if (qacc_env_stride < 0) return fail("dyn: negative stride");
+  return dyn_launch(y, 1, 0, qacc, qacc_env_stride, 0, tau_out, hip_stream);
+}
+extern "C" int dmc_dyn_mul(dmc_dyn* y, const void* vec, int K, void* out, void* hip_stream) {
+  if (!vec) return fail("null argument");
+  if (K < 1) return fail("dyn: at least one vector per environment is needed");
+  return dyn_launch(y, 0, DYN_MUL, vec, 0, K, out, hip_stream);
+}
+extern "C" int dmc_dyn_solve(dmc_dyn* y, const void* vec, int K, void* out, void* hip_stream) {
+  if (!vec) return fail("null argument");
+  if (K < 1) return fail("dyn: at least one right-hand side per environment is needed");
+  return dyn_launch(y, 0, DYN_SOLVE, vec, 0, K, out, hip_stream);
+}

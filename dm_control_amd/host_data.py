@@ -4,7 +4,7 @@ fused kernel never stores, derived from the device's kinematics, and MuJoCo's st
 numpy only, no facade state, every function pure: `c` is a compiled `mjcf_compiler.Model`, everything else arrives as
 arrays (or as a `get(name, *shape)` reader of them).  The functions both facades call (`joint_frames`, `tendons`,
 `object_velocity`, the row helpers) take arbitrary leading batch axes -- `(..., n, 3)` is one environment or `B` of them,
-and the batched result equals the per-environment ones to the bit.  The derivations only `MjData` serves (`mass_matrix`,
+and the batched result equals the per-environment ones to the bit.  The derivations only `MjData` serves (`mass_matrix`, `rne`,
 `passive`, `act_dot`, `subtree_vel`) take one environment.
 
 This module never imports `BatchedPhysics`: tests swap that name in each facade separately, so `create_batch` takes the
@@ -405,6 +405,53 @@ def mass_matrix(c, xpos, xmat, xipos, ximat, xanchor, xaxis):
   M += np.einsum('bki,bi,bli->kl', jl, np.asarray(c.body_inertia, dtype=np.float64), jl)
   M[np.diag_indices(nv)] += np.asarray(c.dof_armature, dtype=np.float64)
   return M
+
+
+def rne(c, qpos, qvel, qacc, xpos, xquat, xipos, ximat):
+  """mj_rne (after mj_comVel) in numpy for one environment: the bias forces c(q, qvel) -- Coriolis, centrifugal, gravity
+  unless disabled -- or, with `qacc`, M qacc + c: inverse dynamics of the rigid-body terms, `dof_armature * qacc`
+  included (mj_rne itself leaves the armature to its callers).  No passive, actuator or constraint force.  Poses arrive
+  as for `mass_matrix` (xpos (nbody, 3), xquat (nbody, 4), xipos, ximat (nbody, 9)); the joint frames are derived from
+  `qpos`.  Spatial vectors are (angular, linear) about the world origin."""
+  nv, nb = c.nv, c.nbody
+  qvel = np.asarray(qvel, dtype=np.float64).ravel()
+  acc = np.zeros(nv) if qacc is None else np.asarray(qacc, dtype=np.float64).ravel()
+  xpos, xquat = np.asarray(xpos, dtype=np.float64).reshape(nb, 3), np.asarray(xquat, dtype=np.float64).reshape(nb, 4)
+  xipos, Ri = np.asarray(xipos, dtype=np.float64).reshape(nb, 3), np.asarray(ximat, dtype=np.float64).reshape(nb, 3, 3)
+  anchor, jaxis = joint_frames(c, np.asarray(qpos, dtype=np.float64), xpos, xquat)
+  axis, point, rot = dof_axes(c, xpos, quat_to_mat_rows(xquat), anchor, jaxis)
+  cdof = np.where(rot[:, None], np.concatenate([axis, cross(axis, -point)], axis=1), np.concatenate([np.zeros((nv, 3)), axis], axis=1))
+  xm = lambda v, w: np.concatenate([np.cross(v[:3], w[:3]), np.cross(v[:3], w[3:]) + np.cross(v[3:], w[:3])])      # v x w (motion)
+  xf = lambda v, f: np.concatenate([np.cross(v[:3], f[:3]) + np.cross(v[3:], f[3:]), np.cross(v[:3], f[3:])])      # v x* f (force)
+
+  def inertia(b, v):      # the body's spatial inertia about the origin times a motion vector
+    m, com = float(c.body_mass[b]), xipos[b]
+    vc = v[3:] + np.cross(v[:3], com)      # the velocity of the centre of mass
+    return np.concatenate([Ri[b] @ (np.asarray(c.body_inertia[b], dtype=np.float64) * (Ri[b].T @ v[:3])) + m * np.cross(com, vc), m * vc])
+  g = np.zeros(3) if int(c.opt.disableflags) & C['DMC_DSBL_GRAVITY'] else np.asarray(c.opt.gravity, dtype=np.float64)
+  cvel, cacc, cfrc = np.zeros((nb, 6)), np.zeros((nb, 6)), np.zeros((nb, 6))
+  cacc[0, 3:] = -g
+  for b in range(1, nb):
+    p = int(c.body_parentid[b])
+    v, a = cvel[p].copy(), cacc[p].copy()
+    for j in range(int(c.body_jntadr[b]), int(c.body_jntadr[b]) + int(c.body_jntnum[b])):
+      t, d = int(c.jnt_type[j]), int(c.jnt_dofadr[j])
+      if t == 0:      # the translations of a free joint: constant axes
+        for k in range(d, d + 3):
+          v += cdof[k] * qvel[k]
+          a += cdof[k] * acc[k]
+        d += 3
+      n = 3 if t in (0, 1) else 1
+      carried = v.copy()      # what carries the joint's axes: everything before the joint (mj_comVel)
+      for k in range(d, d + n):
+        v += cdof[k] * qvel[k]
+        a += xm(carried, cdof[k]) * qvel[k] + cdof[k] * acc[k]
+    cvel[b], cacc[b] = v, a
+    cfrc[b] = inertia(b, a) + xf(v, inertia(b, v))
+  for b in range(nb - 1, 0, -1):
+    cfrc[int(c.body_parentid[b])] += cfrc[b]
+  body = _plan(c, _dof_plan)['body']
+  return np.einsum('ki,ki->k', cdof, cfrc[body]) + np.asarray(c.dof_armature, dtype=np.float64) * acc
 
 
 def passive(c, qpos, qvel):

@@ -1502,6 +1502,58 @@ def mj_applyFT(m, d, force, torque, point, body, qfrc_target):
     q += jr.T @ np.asarray(torque, dtype=np.float64).ravel()
 
 
+def _dynamics_poses(m, d):
+  """(c, qpos, xpos, xquat, xipos, ximat) of one environment as the kinematics stand."""
+  _check(m, d)
+  c = m._c
+  if not d._outputs_valid:
+    d._ensure_forward()
+  get = lambda n, *shape: np.asarray(d._batch.get(n), dtype=np.float64).reshape(shape)
+  xpos, xquat = get('xpos', c.nbody, 3), get('xquat', c.nbody, 4)
+  ximat = host_data.quat_to_mat_rows(host_data.quat_mul_rows(xquat, np.asarray(c.body_iquat, dtype=np.float64).reshape(c.nbody, 4)))
+  return c, d._shadow['qpos'].ravel(), xpos, xquat, get('xipos', c.nbody, 3), ximat
+
+
+def _dense_mass(m, d):
+  c, qpos, xpos, xquat, xipos, ximat = _dynamics_poses(m, d)
+  anchor, axis = host_data.joint_frames(c, qpos, xpos, xquat)
+  return host_data.mass_matrix(c, xpos, host_data.quat_to_mat_rows(xquat), xipos, ximat, anchor, axis)
+
+
+def mj_rne(m, d, flg_acc, result):
+  """mujoco.mj_rne: `result` (nv,) := the bias forces c(qpos, qvel) (mjData.qfrc_bias), plus M qacc with `flg_acc` -- host
+  numpy for one environment (host_data.rne), from the kinematics as they stand.  Unlike MuJoCo's, the `flg_acc` form
+  includes dof_armature * qacc, so that it equals M qacc + c with the M of mj_fullM.  The batch form is
+  dynamics.BatchDynamics.bias / .inverse."""
+  c, qpos, xpos, xquat, xipos, ximat = _dynamics_poses(m, d)
+  r = np.asarray(result).reshape(-1)
+  if r.shape[0] != c.nv:
+    raise FatalError('mj_rne: result must have nv = %d entries' % c.nv)
+  qacc = np.asarray(d.qacc, dtype=np.float64).ravel() if flg_acc else None
+  r[...] = host_data.rne(c, qpos, d._shadow['qvel'].ravel(), qacc, xpos, xquat, xipos, ximat)
+
+
+def mj_mulM(m, d, res, vec):
+  """mujoco.mj_mulM: `res` (nv,) := M vec, M the joint-space inertia at the kinematics as they stand (host numpy; the
+  batch form is dynamics.BatchDynamics.mul)."""
+  M = _dense_mass(m, d)
+  r, v = np.asarray(res).reshape(-1), np.asarray(vec, dtype=np.float64).reshape(-1)
+  if r.shape[0] != M.shape[0] or v.shape[0] != M.shape[0]:
+    raise FatalError('mj_mulM: res and vec must have nv = %d entries' % M.shape[0])
+  r[...] = M @ v
+
+
+def mj_solveM(m, d, x, y, n=None):
+  """mujoco.mj_solveM: `x` (n, nv) := M^-1 y for the n vectors in the rows of `y` (host numpy; the batch form is
+  dynamics.BatchDynamics.solve).  `x` and `y` may be the same array."""
+  M = _dense_mass(m, d)
+  nv = M.shape[0]
+  xs, ys = np.asarray(x), np.asarray(y, dtype=np.float64)
+  if ys.size % nv or xs.size != ys.size or (n is not None and int(n) * nv != ys.size):
+    raise FatalError('mj_solveM: x and y must hold n vectors of nv = %d entries' % nv)
+  xs.reshape(-1, nv)[...] = np.linalg.solve(M, ys.reshape(-1, nv).T).T
+
+
 def mj_integratePos(m, qpos, qvel, dt):
   """utils/inverse_kinematics.py:208: `qpos` advanced in place."""
   q = np.asarray(qpos)
