@@ -95,13 +95,15 @@ class BatchedPhysics:
 
   # -- info ---------------------------------------------------------------------
   def info(self):
-    a = np.zeros(21, dtype=np.int32)
+    a = np.zeros(22, dtype=np.int32)
     _native.check(_native.lib().dmc_batch_info(self._ptr, a.ctypes.data))
     keys = ['B', 'precision', 'lanes_per_env', 'waves_per_block', 'envs_per_block',
             'lds_bytes_per_block', 'grid', 'nconmax', 'njmax', 'env_scratch_bytes', 'static_id',
             'jac_kmax', 'table_lds_bytes', 'envs_per_cu', 'njdense', 'njcon', 'stash', 'stash_bytes_per_env',
             'global_scratch_bytes_per_env', 'work_queue', 'slices']
-    return dict(zip(keys, (int(x) for x in a)))
+    out = dict(zip(keys, (int(x) for x in a)))
+    out['launch'] = {'coop_open': int(a[21])}      # which path a step launch takes (csrc/step_kernel.hip.h: coop_open_phase)
+    return out
 
   def _rows(self, name):
     rows, is_int = ctypes.c_int(), ctypes.c_int()

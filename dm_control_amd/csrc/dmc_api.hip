@@ -22,6 +22,7 @@ hipError_t launch_step_f32(const LaunchGeom& g, hipStream_t stream, const StepLa
                            const int* g_mi, const float* g_mr, const int* g_mc, const StepIO<float>& io, int nstep, int legacy, int mode, int outmask, int nsub);
 hipError_t launch_step_f64(const LaunchGeom& g, hipStream_t stream, const StepLayout* d_layout, const StepOpts<double>& o,
                            const int* g_mi, const double* g_mr, const int* g_mc, const StepIO<double>& io, int nstep, int legacy, int mode, int outmask, int nsub);
+int step_coop_open_f32(const LaunchGeom& g);
 }  // namespace dmc
 
 using namespace dmc;
@@ -109,7 +110,7 @@ struct dmc_batch {
   int* d_eg_slot = nullptr;      // per-env world geoms: (ngeom) slot table on the device (field F_env_geom holds the values)
   // a model-specialised kernel built on demand for this model (dmc_batch_attach_specialised): the loaded object, its launch
   // entry, whether it holds the optional launch features (step_core.h kFeat)
-  void* spec_so = nullptr; void* spec_launch = nullptr; int spec_features = 0;
+  void* spec_so = nullptr; void* spec_launch = nullptr; int spec_features = 0; int spec_coop = 0;
   int spec_task_bytes = 0;      // > 0: the attached kernel carries a task epilogue with an argument block of this size
   void* d_task_args = nullptr; int task_on = 0;      // its arguments on the device; whether the next step launches run it
 };
@@ -541,6 +542,8 @@ extern "C" int dmc_batch_attach_specialised(dmc_batch* b, const char* so_path) {
   typedef int (*tb_t)();
   tb_t tb = (tb_t)dlsym(h, "dmc_spec_task_args_bytes");
   b->spec_task_bytes = tb ? tb() : 0;
+  tb_t fc = (tb_t)dlsym(h, "dmc_spec_coop_open");
+  b->spec_coop = fc ? fc() : 0;
   b->task_on = 0;
   // the record of the kinematic stash is the kernel's choice (StepCore::krec: packed in a -DDMC_NO_WIDE_IO build): what
   // the kernel that ran so far left behind is not for the one that runs from here on
@@ -1184,6 +1187,10 @@ extern "C" int dmc_batch_info(const dmc_batch* b, int* info) {
   info[18] = (int)((size_t)L.n_gs * b->elem);
   info[19] = b->geom.queue;
   info[20] = b->geom.queue ? b->max_slices : 0;      // pieces a queued Physics.step(nstep > 1) launch cuts an item into, at most (<= 1: whole items)
+  // 1: the batch's step launches open with the stage split across wave pairs (step_kernel_body's `coop`: a kernel that has
+  // it, whole wave pairs per workgroup, no work queue, a kinematic stash and no full stash)
+  const int coop_kernel = b->spec_launch ? b->spec_coop : (b->precision == 32 ? step_coop_open_f32(b->geom) : 0);
+  info[21] = (coop_kernel && b->geom.waves % 2 == 0 && !b->geom.queue && b->d_kstash && !b->stash_on) ? 1 : 0;
   return 0;
 }
 

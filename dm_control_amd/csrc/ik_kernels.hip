@@ -140,7 +140,7 @@ int launch_ik(const dmc_ik* ik, const void* tpos, const void* tquat, const void*
 extern "C" int dmc_ik_create(dmc_batch* b, const dmc_ik_chain* c, const dmc_ik_options* opt, dmc_ik** out) {
   if (!b || !c || !opt || !out) return ik_fail("dmc_ik_create: null argument");
   *out = nullptr;
-  int info[21] = {0};
+  int info[22] = {0};
   if (dmc_batch_info(b, info) != 0) return ik_fail(std::string("dmc_ik_create: ") + dmc_last_error());
   int nq = 0, is_int = 0;
   if (dmc_batch_field_rows(b, "qpos", &nq, &is_int) != 0 || is_int) return ik_fail("dmc_ik_create: the batch has no qpos");

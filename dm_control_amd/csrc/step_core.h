@@ -5195,6 +5195,39 @@ struct StepCore {
     if (!skipsensor) sensors(DMC_STAGE_VEL);
     DMC_PROF(PROF_SENS);
   }
+  // ---- the opening stage split by function across a wave pair (step_kernel.hip.h: coop_open_phase) --------------------------
+  // With the kinematics taken from the stash, the opening stage of a launch is stage_posvel(false, .., true, true): the
+  // mass matrix and its factor, the bias forces, the contacts and the constraint rows.  They form two sides that depend on
+  // the kinematics alone and meet only in LDS: A writes qM, qLH and the qfrc_bias / qfrc_passive rows and owns the overlay
+  // region (crb / mbuf, then cacc / cfrc / cfrc_ext: hence A holds both, in this order); B writes the contact and
+  // constraint arrays, the row counts and warning counters of `imisc`, and nothing of the overlays.  Neither reads what
+  // the other writes (tests/test_coop_open_cpu.py runs them in both orders), so two waves may run them at the same time.
+  // The kernels of the small dense models that hold two 32-lane environments per wave do that in their queue-less
+  // launches: waves 2k and 2k + 1 of a workgroup take one side each for the pair's four environments at 16 lanes per
+  // environment, so that each wave issues about half of the stage's instructions.  -DDMC_NO_COOP_OPEN: the owner wave runs
+  // the stage alone, as before (tests/test_gpu_coop_open.py builds against it).
+  DMC_DEV void coop_side_a() { crb_mass_matrix(); passive_and_rne(); }
+  DMC_DEV void coop_side_b() { collision(); make_constraint(); }
+  // `misc` slot kMiscCoop, written for every environment slot of the workgroup in front of the sides: kCoopEntered = run()'s
+  // prologue and the first pass's check_pos_vel are done (coop_prelude), kCoopOpened = the sides run the opening stage.
+  static constexpr int kMiscCoop = 3, kCoopOpened = 1, kCoopEntered = 2;
+#if !defined(DMC_HOST_EMU) && !defined(DMC_NO_COOP_OPEN) && !defined(DMC_PROFILE) && !defined(DMC_TRACE_SUB)
+  static constexpr bool kCoopOpen = kAccRegs && LPE == 32;
+#else
+  static constexpr bool kCoopOpen = false;      // (the phase counters and the sub-stage trace belong to one wave per environment)
+#endif
+  // run() up to the opening stage of its first pass, for an environment whose first pass is a plain full stage on stashed
+  // kinematics -- the statements of run() in run()'s order -- and nothing for any other environment (launch override,
+  // stash miss, RK4 ...: returns 0 and the owner wave runs the whole of run() behind the sides).
+  DMC_DEV int coop_prelude(const StepIO<T>& io, int env, int nstep, int legacy, int mode, const Entry& en) {
+    if (io.env_mode && en.em != 0) return 0;
+    if (!(mode == 0 && nstep >= 1 && legacy && io.kstash && !io.stash_r && o.integrator != DMC_INT_RK4 && en.fast && en.kvalid)) return 0;
+    if (lane == 0) set_epoch(en.epoch);
+    load_state(io, env, false, en);
+    DMC_WSYNC();
+    kstash_env_geoms();
+    return check_pos_vel() ? kCoopEntered : (kCoopEntered | kCoopOpened);      // (a reset state has no stashed kinematics)
+  }
   // Acceleration stage (mj_step2 without the integrator)
   // euler_next: the caller integrates this pass with call_euler() next (not an RK4 stage, not mj_forward)
   DMC_DEV void stage_acc(bool disable_actuation, bool skipsensor, bool euler_next = false) {
@@ -5363,13 +5396,22 @@ struct StepCore {
   // of an env that the launch override turned into mj_forward.  Every pass
   // rebuilds its derived arrays from (qpos, qvel, act, qacc_warmstart, time), so a cut between the integration of one
   // physics step and the position stage of the next recomputes nothing.
-  DMC_DEV void run(const StepIO<T>& io, int env, int nstep, int legacy, int mode, int outmask, int nsub, const Entry& en,
-                   int piece = 0, int npieces = 1) {
+  // ph (kernels with kCoopOpen only, see coop_prelude): 0 = the whole call; 1 = only what precedes the opening stage of an
+  // environment that takes the cooperative route, returning its `misc` flag; 2 = the rest of the call after a ph 1 call
+  // on the same object (which is the whole call when that one returned 0).
+  DMC_DEV int run(const StepIO<T>& io, int env, int nstep, int legacy, int mode, int outmask, int nsub, const Entry& en,
+                  int piece = 0, int npieces = 1, int ph = 0) {
     const int launch_mode = mode;
-    if (lane == 0) set_epoch(en.epoch);      // (kept in LDS, not in a register, for the whole launch)
+    int cst = 0;
+    if constexpr (kCoopOpen) {
+      if (ph == 1) return coop_prelude(io, env, nstep, legacy, mode, en);
+      if (ph == 2) cst = (int)S(misc)[kMiscCoop];
+    }
+    const bool resumed = kCoopOpen && (cst & kCoopEntered);      // (such an environment has no launch override, no full stash)
+    if (!resumed) { if (lane == 0) set_epoch(en.epoch); }      // (kept in LDS, not in a register, for the whole launch)
     if (io.env_mode) {
       const int em = en.em;
-      if (em == 2) return;
+      if (em == 2) return 0;
       if (em == 1 && (mode == 0 || mode >= 4)) mode = 2;
     }
     if constexpr (!kSlices) { piece = 0; npieces = 1; }
@@ -5378,20 +5420,22 @@ struct StepCore {
     // LDS slot), so the arrays must be computed here and not by whichever wave claimed piece 0.  The earlier pieces do
     // nothing (the kernel still publishes the item's progress for them), and the pass loads from the state arrays: no
     // piece wrote a hand-off record.
-    if (mode != 0 && piece != npieces - 1) return;
+    if (mode != 0 && piece != npieces - 1) return 0;
     if (mode != 0) { piece = 0; npieces = 1; }
-    if (mode >= 4) { run_split(io, env, mode, outmask, en); return; }
+    if (mode >= 4) { run_split(io, env, mode, outmask, en); return 0; }
     prof_begin();
     const bool stash = io.stash_r != nullptr;
     bool have = false;
     if (stash && mode == 0 && legacy && o.integrator != DMC_INT_RK4) have = load_stash(io, env);
-    load_state(io, env, have, en, kSlices && piece > 0);
+    if (!resumed) load_state(io, env, have, en, kSlices && piece > 0);
     bool havekin = false;
     // (the stash was only prefetched for a launch that steps: an env switched to mj_forward by env_mode has none)
-    if (piece == 0 && io.kstash && mode == 0 && launch_mode == 0 && legacy && !have && o.integrator != DMC_INT_RK4) {
+    if (!resumed && piece == 0 && io.kstash && mode == 0 && launch_mode == 0 && legacy && !have && o.integrator != DMC_INT_RK4) {
       if (!en.fast) havekin = load_kstash(io, env);
       else if (en.kvalid) { havekin = true; DMC_WSYNC(); kstash_env_geoms(); }
     }
+    // (resumed: the first pass's check_pos_vel ran in coop_prelude; kCoopOpened: so did its opening stage, on the two sides)
+    const bool opened = resumed && (cst & kCoopOpened);
     DMC_PROF(PROF_LOAD);
     const bool stepping = mode == 0 || mode == 3;
     const int ntotal = mode == 3 ? nstep*nsub : nstep;
@@ -5409,7 +5453,7 @@ struct StepCore {
       const bool trailing = stepping && it == ntotal;
       const bool partial = trailing && !(stash && mode == 0) && !fwd_after;
       if (mode == 3 && !trailing && it % nsub == 0 && io.ctrl_seq) load_ctrl_seq(io, env, it / nsub);
-      if (stepping) { if (check_pos_vel()) { have = false; havekin = false; } }
+      if (stepping && !(resumed && it == 0)) { if (check_pos_vel()) { have = false; havekin = false; } }
       const int nstage = (stepping && !trailing && o.integrator == DMC_INT_RK4) ? 4 : 1;
       // Sensor values are overwritten by every step, so only the passes whose sensordata can be
       // read afterwards evaluate them: position/velocity sensors in the last pass of a launch and
@@ -5418,7 +5462,7 @@ struct StepCore {
       const bool sens_acc = !stepping || (it == ntotal - 1 && !fwd_after) || (trailing && fwd_after) || (mode == 3 && (it + 1) % nsub == 0);
       int stage = 0, retried = 0;
       while (stage < nstage) {
-        if (!(have && it == 0 && !retried)) call_posvel(partial, outmask, stage > 0 || !sens_pv, havekin && it == 0 && !retried && !trailing);
+        if (!((have || opened) && it == 0 && !retried)) call_posvel(partial, outmask, stage > 0 || !sens_pv, havekin && it == 0 && !retried && !trailing);
         if (it == 0 && stage == 0) trace_stamp(io, env, 4); else if (trailing) trace_stamp(io, env, 7);
         if (mode == 3 && stage == 0 && it > 0 && it % nsub == 0) store_seq(io, env, it / nsub - 1);
         if (mode == 0 && stage == 0 && it >= 1) probe_store(io, env, it - 1, 1);      // the state after `it` physics steps
@@ -5439,7 +5483,7 @@ struct StepCore {
       if (it == 0) trace_stamp(io, env, 6);
       DMC_PROF(PROF_EULER);
     }
-    if constexpr (kSlices) if (!last_piece) { store_handoff(io, env); DMC_PROF(PROF_STORE); prof_end(io, env); return; }      // (the next piece takes it from here)
+    if constexpr (kSlices) if (!last_piece) { store_handoff(io, env); DMC_PROF(PROF_STORE); prof_end(io, env); return 0; }      // (the next piece takes it from here)
     if (!stepping) dump_debug(io, env);
     // an environment the launch override turned into mj_forward (just re-initialised) reports its one state in every slot
     if (!stepping && launch_mode == 0) probe_store(io, env, 0, nstep);
@@ -5453,6 +5497,7 @@ struct StepCore {
     store_state(io, env, kWideIO);
     DMC_PROF(PROF_STORE);
     prof_end(io, env);
+    return 0;
   }
 #undef MI
 #undef MR
@@ -5472,6 +5517,19 @@ struct StageFns {
                             DMC_LDS int* si, int lane, int flags, int outmask) {
     Core c(ls, *(const StepOpts<T>*)o, (const int*)mi, (const T*)mr, gc, (T*)s, (int*)si, lane);
     c.stage_posvel(flags & 1, outmask, flags & 2, flags & 4);
+  }
+  // the two sides of the cooperative opening stage, on SIXTEEN lanes per environment whatever LPE is: s / si are the
+  // scratch of the environment this lane's 16-lane row works for, `on` whether that environment takes part
+  typedef StepCore<T, 16, LS> Core16;
+  static DMC_FN void coop_a(LS ls, const DMC_LDS StepOpts<T>* o, DMC_LDS int* mi, DMC_LDS T* mr, const int* gc, DMC_LDS T* s,
+                            DMC_LDS int* si, int lane, int on) {
+    Core16 c(ls, *(const StepOpts<T>*)o, (const int*)mi, (const T*)mr, gc, (T*)s, (int*)si, lane);
+    if (on) c.coop_side_a();
+  }
+  static DMC_FN void coop_b(LS ls, const DMC_LDS StepOpts<T>* o, DMC_LDS int* mi, DMC_LDS T* mr, const int* gc, DMC_LDS T* s,
+                            DMC_LDS int* si, int lane, int on) {
+    Core16 c(ls, *(const StepOpts<T>*)o, (const int*)mi, (const T*)mr, gc, (T*)s, (int*)si, lane);
+    if (on) c.coop_side_b();
   }
   static DMC_FN void acc(LS ls, const DMC_LDS StepOpts<T>* o, DMC_LDS int* mi, DMC_LDS T* mr, const int* gc, DMC_LDS T* s,
                          DMC_LDS int* si, int lane, int flags) {

@@ -65,6 +65,37 @@ template <typename T> constexpr int kernarg_io_offset(int karg0) {
 }
 #endif
 
+// The cooperative opening stage (step_core.h: coop_side_a / coop_side_b) of the kernels with StepCore::kCoopOpen.  Called by
+// EVERY wave of the workgroup exactly once per launch, from wave-uniform control flow, with the flag of the lane's own
+// environment slot (run(.., ph = 1); 0 for a slot without an environment): flags out, barrier, one side for the four
+// environment slots of the wave pair at 16 lanes each -- the even wave side A, the odd one side B --, barrier.  `envs`:
+// the workgroup's first environment slot.
+template <typename T, int LPE, typename LS>
+__device__ __forceinline__ void coop_open_phase(LS ls, const StepOpts<T>* o_lds, int* mi, T* mr, const int* gc, unsigned char* envs,
+                                                size_t env_bytes, int st) {
+  typedef StepCore<T, LPE, LS> Core;
+  static_assert(LPE == 32, "a wave pair holds four environments, a wave four 16-lane rows");
+  const StepLayout& L = ls.get();
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  if (t % LPE == 0) reinterpret_cast<T*>(envs + (size_t)(t / LPE) * env_bytes)[L.s_misc + Core::kMiscCoop] = (T)st;
+  __syncthreads();
+  {
+    const int slot = ((t >> 6) & ~1) * (64 / LPE) + ((t & 63) >> 4);
+    unsigned char* base = envs + (size_t)slot * env_bytes;
+    T* s = reinterpret_cast<T*>(base);
+    int* si = reinterpret_cast<int*>(base + (size_t)L.n_sr * sizeof(T));
+    const int on = (int)s[L.s_misc + Core::kMiscCoop] & Core::kCoopOpened;
+    if (__builtin_amdgcn_ballot_w64(on != 0)) {      // (a pair without a participating environment: straight to the barrier)
+      if (__builtin_amdgcn_readfirstlane(t >> 6) & 1)
+        StageFns<T, LPE, LS>::coop_b(ls, (const DMC_LDS StepOpts<T>*)o_lds, (DMC_LDS int*)mi, (DMC_LDS T*)mr, gc, (DMC_LDS T*)s, (DMC_LDS int*)si, t & 15, on);
+      else
+        StageFns<T, LPE, LS>::coop_a(ls, (const DMC_LDS StepOpts<T>*)o_lds, (DMC_LDS int*)mi, (DMC_LDS T*)mr, gc, (DMC_LDS T*)s, (DMC_LDS int*)si, t & 15, on);
+    }
+  }
+  __syncthreads();
+}
+
 // QUEUE = false: every wave has exactly one item (the batch fits the resident grid) -- no claim loop, so nothing of
 // the body is "loop invariant": with the loop the kernel arguments are hoisted out of it, spilled to VGPR lanes
 // (106 SGPRs hold a fraction of StepIO's ~60 pointers) and read back with v_readlane where they are used.
@@ -143,6 +174,12 @@ __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg
   int* const head = (QUEUE && q_work) ? q_work + 32 * (1 + xq) : nullptr;      // (a 128-byte line per head)
   int slot = lblk * wpb + wave, piece = 0;
   bool have_item = slot < nitems;
+  // The cooperative opening stage (coop_open_phase) holds two workgroup barriers that every wave of the workgroup must
+  // meet, so whether a launch has it is decided from kernel arguments, blockDim and template parameters ALONE -- one
+  // answer for every wave of the launch: whole wave pairs, and a stepping launch whose environments can have stashed
+  // kinematics.  What an environment does with it is decided per environment, by flags in LDS (coop_prelude).
+  const bool coop = Core::kCoopOpen && !QUEUE && (nthr & 127) == 0 && mode == 0 && legacy && nstep >= 1 && io_arg.kstash && !io_arg.stash_r;
+  (void)coop;
   if (QUEUE && head) {
     int nx = 0;
     if ((tid & 63) == 0) nx = atomicAdd(head, 1);
@@ -247,7 +284,16 @@ __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg
     const long long tw1 = tr ? (long long)wall_clock64() : 0;
     const long long t0 = io.cost ? (long long)__builtin_readcyclecounter() : 0;
     if (tr && (threadIdx.x & 63) == 0 && piece == 0) { tr[item] = t_entry; tr[nitems + item] = (int)(wall_clock64() & 0x7fffffffll); }
-    if (env < io.B) core.run(io, env, nstep, legacy, mode, outmask, nsub, en, piece, npieces);
+    if constexpr (Core::kCoopOpen && !QUEUE) {
+      if (coop) {
+        int st = 0;
+        if (env < io.B) st = core.run(io, env, nstep, legacy, mode, outmask, nsub, en, piece, npieces, 1);
+        coop_open_phase<T, LPE, LS>(ls, o_lds, mi, mr, L.d.coldlds ? (const int*)mc_lds : g_mc, tables + tables_bytes, env_bytes, st);
+      }
+      if (env < io.B) core.run(io, env, nstep, legacy, mode, outmask, nsub, en, piece, npieces, coop ? 2 : 0);
+    } else {
+      if (env < io.B) core.run(io, env, nstep, legacy, mode, outmask, nsub, en, piece, npieces);
+    }
 #ifdef DMC_TASK_HEADER
     // the generated task layer of this model's task (suite/fused_env.py), by one lane per environment: it reads what the
     // launch has just stored (loads that bypass the L1, after the wave's stores are acknowledged)
@@ -290,6 +336,9 @@ __device__ __forceinline__ void step_kernel_body(LS ls, const StepOpts<T>& o_arg
     if (nenv >= io.B) nenv = io.B - 1;
     // (later items load in place, inside run(): up here the registers are full of what the loop keeps alive)
     en.em = io.env_mode ? io.env_mode[nenv] : 0; en.fast = 0; en.kvalid = 0;
+  } else if constexpr (Core::kCoopOpen && !QUEUE) {
+    // (a wave without an item: its environment slots take no part, its lanes work for the partner's, and it meets the barriers)
+    if (coop) coop_open_phase<T, LPE, LS>(ls, o_lds, mi, mr, L.d.coldlds ? (const int*)mc_lds : g_mc, tables + tables_bytes, env_bytes, 0);
   }
   if (QUEUE && q_work && (threadIdx.x & 63) == 0) {
     // every wave makes exactly one failing claim before it gets here, so the last wave to arrive can re-arm the queues
@@ -391,6 +440,19 @@ static hipError_t launch_step_t(const LaunchGeom& g, hipStream_t stream, const S
 #undef DMC_LAUNCH_Q
 #undef DMC_LAUNCH_STATIC_Q
   return hipGetLastError();
+}
+
+// 1: the kernel launch_step_t picks for this geometry is a model-specialised one of this unit with the cooperative opening
+// stage compiled in (StepCore::kCoopOpen); which of its launches take it is step_kernel_body's `coop`
+template <typename T>
+static int step_kernel_coop_open(const LaunchGeom& g) {
+#if DMC_NSTATIC > 0
+#define DMC_X(SID, LPE) if (g.static_id == SID && g.lpe == LPE) return StepCore<T, LPE, StaticLayout<SID>>::kCoopOpen ? 1 : 0;
+  DMC_UNIT_INSTANCES(DMC_X)
+#undef DMC_X
+#endif
+  (void)g;
+  return 0;
 }
 
 }  // namespace dmc

@@ -15,4 +15,6 @@ hipError_t launch_step_f32(const LaunchGeom& g, hipStream_t stream, const StepLa
 #endif
   return launch_step_t<float>(g, stream, d_layout, o, g_mi, g_mr, g_mc, io, nstep, legacy, mode, outmask, nsub);
 }
+// (dmc_batch_info: the large models' kernels and the generic ones have no cooperative opening stage)
+int step_coop_open_f32(const LaunchGeom& g) { return step_kernel_coop_open<float>(g); }
 }  // namespace dmc

@@ -315,10 +315,10 @@ int dmc_camera_set_tuning(dmc_camera* c, int cull, int pretransform);
  * the cameras read, did so when the last step / forward launch ran, or no such launch has run yet. */
 int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_dev, void* seg_dev, void* hip_stream);
 
-/* info[0..20] = {B, precision, lanes_per_env, waves_per_block, envs_per_block,
+/* info[0..21] = {B, precision, lanes_per_env, waves_per_block, envs_per_block,
  * lds_bytes_per_block, grid, nconmax, njmax, env_scratch_bytes, static_id,
  * jac_kmax, table_lds_bytes, envs_per_cu, njdense, njcon, stash_on, stash_bytes_per_env,
- * global_scratch_bytes_per_env, work_queue, slices}
+ * global_scratch_bytes_per_env, work_queue, slices, coop_open}
  * (static_id >= 0: a model-specialised kernel instantiation is in use; jac_kmax: entries per
  * compressed contact Jacobian row; envs_per_cu: environments resident on one CU under the
  * 160 KiB LDS budget; global_scratch_bytes_per_env: what a tree-sparse model (nv > 16) keeps in
@@ -331,7 +331,9 @@ int dmc_camera_render(dmc_camera* c, int what_mask, void* rgb_dev, void* depth_d
  * instead of within one env-step: trajectories bit-identical, config 4 460 k -> 577 k env-steps/s.  DMC_SLICES=1
  * restores whole items); slices: the most pieces such a launch cuts an environment's steps into -- 0 without a work
  * queue, 1 where the device's L2 arrangement keeps whole items, DMC_SLICES where set.  Models of at most 16 dofs are
- * never cut). */
+ * never cut); coop_open: 1 when the batch's step launches run the opening stage split by function across the wave
+ * pairs of a workgroup -- the fp32 kernels specialised for the small dense models, workgroups of whole wave pairs, no
+ * work queue, the kinematic stash on and the full stash off). */
 int dmc_batch_info(const dmc_batch* b, int* info);
 
 /* Profiling contract.  Replaces: Physics.enable_profiling() -> wrapper.enable_timer(True), which installs mjcb_time
