@@ -40,6 +40,9 @@ JAC_EXPORTS = ['dmc_jac_create', 'dmc_jac_jacobian', 'dmc_jac_velocity', 'dmc_ja
 DYN_EXPORTS = ['dmc_dyn_create', 'dmc_dyn_mass_matrix', 'dmc_dyn_bias', 'dmc_dyn_inverse', 'dmc_dyn_mul', 'dmc_dyn_solve', 'dmc_dyn_info',
                'dmc_dyn_destroy']
 
+# include/dmc_lin.h (batched linearisation: csrc/lin_kernels.hip)
+LIN_EXPORTS = ['dmc_lin_create', 'dmc_lin_transition', 'dmc_lin_fan_out', 'dmc_lin_warnings', 'dmc_lin_info', 'dmc_lin_destroy']
+
 _lib = None
 
 
@@ -170,6 +173,14 @@ def lib():
     L.dmc_dyn_info.argtypes = [vp, vp]
     L.dmc_dyn_destroy.argtypes = [vp]
     L.dmc_dyn_destroy.restype = None
+  if hasattr(L, 'dmc_lin_create'):
+    L.dmc_lin_create.argtypes = [vp, vp, vp, cd, ci, ci, ctypes.POINTER(vp)]
+    L.dmc_lin_transition.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+    L.dmc_lin_fan_out.argtypes = [vp, ci, ci, vp]
+    L.dmc_lin_warnings.argtypes = [vp, vp, vp]
+    L.dmc_lin_info.argtypes = [vp, vp]
+    L.dmc_lin_destroy.argtypes = [vp]
+    L.dmc_lin_destroy.restype = None
   _lib = L
   return L
 

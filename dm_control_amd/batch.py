@@ -27,6 +27,7 @@ class BatchedPhysics:
     L = _native.lib()
     self.model = model
     self.model_real = {}      # the host's record of what set_model_real wrote: {name: values}
+    self.opts = {}            # ... and of what set_opt wrote: {name: value} (linearize.BatchLinearization replays both)
     self.batch_size = int(batch_size)
     self.precision = precision
     self.device_id = device_id
@@ -217,6 +218,7 @@ class BatchedPhysics:
       _native.check(L.dmc_batch_set_opt_int(self._ptr, name.encode(), int(value)))
     else:
       _native.check(L.dmc_batch_set_opt_real(self._ptr, name.encode(), float(value)))
+    self.opts[name] = value
 
   def set_model_real(self, name, values):
     """Rewrites a model constant shared by the whole batch (see dmc_batch_set_model_real)."""

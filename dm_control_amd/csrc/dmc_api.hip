@@ -2126,3 +2126,146 @@ extern "C" int dmc_dyn_solve(dmc_dyn* y, const void* vec, int K, void* out, void
   if (K < 1) return fail("dyn: at least one right-hand side per environment is needed");
   return dyn_launch(y, 0, DYN_SOLVE, vec, 0, K, out, hip_stream);
 }
+
+// ---- batched linearisation (lin_core.h, lin_kernels.hip; include/dmc_lin.h) -----------------------------------------
+#include "../../include/dmc_lin.h"
+#include "lin_core.h"
+struct dmc_lin {
+  dmc_batch *src, *scr;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
+  LinDims d;
+  int P, nstep;
+  double eps;
+  int* d_ints;
+  double* d_reals;    // ctrlrange, fp64 in every precision pair
+  int* d_flags;       // (B, nu)
+  int* d_warn;        // (B)
+};
+extern "C" int dmc_lin_create(dmc_batch* src, dmc_batch* scr, const dmc_lin_tables* tb, double eps, int centered, int nstep,
+                              dmc_lin** out) {
+  if (!src || !scr || !tb || !out || !tb->ints) return fail("null argument");
+  *out = nullptr;
+  if (src == scr) return fail("lin: the scratch batch must be a batch of its own");
+  const HostModel &m = src->model->hm, &ms = scr->model->hm;
+  if (src->device != scr->device) return fail("lin: the scratch batch must live on the source batch's device");
+  if (ms.nq != m.nq || ms.nv != m.nv || ms.na != m.na || ms.nu != m.nu || ms.njnt != m.njnt || ms.nbody != m.nbody ||
+      ms.nmocap != m.nmocap || ms.nsensordata != m.nsensordata)
+    return fail("lin: the scratch batch must hold the source batch's model");
+  if (scr->precision < src->precision) return fail("lin: an fp32 scratch batch cannot linearise an fp64 batch");
+  if (src->tb.opts.eg_n) return fail("lin: the source batch declares per-environment geoms, which are not mirrored to the scratch batch");
+  if (!(eps > 0) || !std::isfinite(eps)) return fail("lin: eps must be positive");
+  if (nstep < 1) return fail("lin: nstep must be >= 1");
+  if (tb->nj != m.njnt || tb->nq != m.nq || tb->nv != m.nv || tb->na != m.na || tb->nu != m.nu) return fail("lin: the table sizes must be the model's");
+  LinDims d = {m.njnt, m.nq, m.nv, m.na, m.nu, m.nbody, m.nmocap, m.nsensordata, 0, centered ? 1 : 0};
+  if (lin_nx(d) < 1) return fail("lin: the model has no state (nx = 0)");
+  if (tb->nints != lin_nints(d) || tb->nreals != lin_nreals(d) || (tb->nreals && !tb->reals)) return fail("lin: the tables do not have the length their sizes say");
+  // every address the kernels follow is checked here, once
+  const LinTab t = lin_tab(d, tb->ints, tb->reals);
+  static const int qw[4] = {7, 4, 1, 1}, dw[4] = {6, 3, 1, 1};
+  std::vector<int> qseen(d.nq, 0), dseen(d.nv, 0);
+  for (int j = 0; j < d.nj; j++) {
+    const int ty = t.jnt_type[j];
+    if (ty < 0 || ty > 3) return fail("lin: unknown joint type");
+    if (t.jnt_qadr[j] < 0 || t.jnt_qadr[j] + qw[ty] > d.nq) return fail("lin: qpos address outside the model");
+    if (t.jnt_dadr[j] < 0 || t.jnt_dadr[j] + dw[ty] > d.nv) return fail("lin: dof address outside the model");
+    for (int i = 0; i < qw[ty]; i++) qseen[t.jnt_qadr[j] + i]++;
+    for (int i = 0; i < dw[ty]; i++) dseen[t.jnt_dadr[j] + i]++;
+  }
+  for (int k = 0; k < d.nq; k++) if (qseen[k] != 1) return fail("lin: every qpos entry must belong to exactly one joint");
+  for (int k = 0; k < d.nv; k++) if (dseen[k] != 1) return fail("lin: every dof must belong to exactly one joint");
+  for (int k = 0; k < d.nu; k++) {
+    if (t.ctrllimited[k] != 0 && t.ctrllimited[k] != 1) return fail("lin: ctrllimited is 0 or 1");
+    if (!std::isfinite(t.ctrlrange[2*k]) || !std::isfinite(t.ctrlrange[2*k + 1])) return fail("lin: a table entry is not finite");
+  }
+  const int P = lin_ncol(d);
+  if (scr->B < P) return fail("lin: the scratch batch holds " + std::to_string(scr->B) + " environments, one linearisation needs " + std::to_string(P));
+  HIP_TRY(hipSetDevice(src->device));
+  dmc_lin* l = new dmc_lin();      // (zeroed)
+  l->src = src; l->scr = scr; l->d = d; l->P = P; l->nstep = nstep; l->eps = eps;
+  int rc = dev_alloc(l, &l->d_ints, sizeof(int)*(size_t)std::max(1, tb->nints), false, "lin int tables", tb->nints ? tb->ints : nullptr);
+  std::vector<double> reals(tb->reals, tb->reals + tb->nreals);
+  reals.push_back(0);      // (never empty)
+  rc = rc ? rc : dev_alloc(l, &l->d_reals, sizeof(double)*reals.size(), false, "lin real tables", reals.data());
+  rc = rc ? rc : dev_alloc(l, &l->d_flags, sizeof(int)*(size_t)src->B*std::max(1, d.nu), true, "lin nudge flags");
+  rc = rc ? rc : dev_alloc(l, &l->d_warn, sizeof(int)*(size_t)src->B, true, "lin warnings");
+  if (rc) { dmc_lin_destroy(l); return rc; }
+  *out = l;
+  return 0;
+}
+extern "C" void dmc_lin_destroy(dmc_lin* l) {
+  if (!l) return;
+  dev_free_all(l);
+  delete l;
+}
+extern "C" int dmc_lin_info(const dmc_lin* l, int* info) {
+  if (!l || !info) return fail("null argument");
+  const int v[12] = {l->src->B, l->P, lin_nx(l->d), l->d.nu, l->d.nsensordata, l->scr->B, l->scr->B/l->P, l->src->precision,
+                     l->scr->precision, l->nstep, l->d.centered, kLinBlock};
+  for (int k = 0; k < 12; k++) info[k] = v[k];
+  return 0;
+}
+extern "C" int dmc_lin_warnings(dmc_lin* l, int32_t* warn_out, void* hip_stream) {
+  if (!l || !warn_out) return fail("null argument");
+  HIP_TRY(hipSetDevice(l->src->device));
+  HIP_TRY(hipMemcpyAsync(warn_out, l->d_warn, sizeof(int)*(size_t)l->src->B, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+  return 0;
+}
+template <typename Ts, typename Tc>
+static void lin_fill(dmc_lin* l, LinArgs<Ts, Tc>* a) {
+  static const FieldId ids[LIN_NFIELD] = {F_qpos, F_qvel, F_act, F_ctrl, F_qacc_warmstart, F_qfrc_applied, F_xfrc_applied, F_mocap_pos,
+                                          F_mocap_quat, F_sensordata};
+  *a = LinArgs<Ts, Tc>();
+  a->d = l->d; a->d.xfrc = l->src->xfrc_on ? 1 : 0;
+  a->ints = l->d_ints; a->reals = l->d_reals;
+  for (int f = 0; f < LIN_NFIELD; f++) {      // (every call: a field can be rebound)
+    a->src[f] = (const Ts*)l->src->fields[ids[f]].dev;
+    a->scr[f] = (Tc*)l->scr->fields[ids[f]].dev;
+  }
+  a->src_time = (const double*)l->src->fields[F_time].dev; a->scr_time = (double*)l->scr->fields[F_time].dev;
+  a->scr_warning = (int*)l->scr->fields[F_warning].dev;
+  a->flags = l->d_flags; a->warn = l->d_warn;
+  a->B = l->src->B; a->Bs = l->scr->B; a->P = l->P;
+  a->eps = (Tc)l->eps; a->ch = (Tc)cos(0.5*l->eps); a->sh = (Tc)sin(0.5*l->eps);
+}
+// fan_only: the first launch of a transition alone (dmc_lin_fan_out)
+static int lin_run(dmc_lin* l, int first_env, int nenv, void* A, void* Bm, void* C, void* D, void* hip_stream, bool fan_only) {
+  if (!l || (!fan_only && (!A || (!Bm && l->d.nu)))) return fail("null argument");
+  if ((C == nullptr) != (D == nullptr) && l->d.nu) return fail("lin: C and D come together");
+  if (C && !(l->scr->outmask & OUT_SENSOR)) return fail("lin: sensor derivatives need the sensors in the scratch batch's output mask");
+  if (nenv < 1 || first_env < 0 || (long long)first_env + nenv > l->src->B) return fail("lin: the chunk lies outside the source batch");
+  if ((long long)nenv*l->P > l->scr->B)
+    return fail("lin: " + std::to_string(nenv) + " environments need " + std::to_string((long long)nenv*l->P) + " scratch environments, the scratch batch holds " +
+                std::to_string(l->scr->B));
+  HIP_TRY(hipSetDevice(l->src->device));
+  auto run = [&](auto zs, auto zc) {
+    using Ts = decltype(zs);
+    using Tc = decltype(zc);
+    LinArgs<Ts, Tc> a;
+    lin_fill(l, &a);
+    a.first_env = first_env; a.nenv = nenv;
+    a.A = (Ts*)A; a.Bm = (Ts*)Bm; a.C = (Ts*)C; a.D = (Ts*)D;
+    auto go = [&](int which) {
+      if constexpr (std::is_same_v<Tc, float>) return launch_lin_f32_f32(a, which, hip_stream);
+      else if constexpr (std::is_same_v<Ts, float>) return launch_lin_f32_f64(a, which, hip_stream);
+      else return launch_lin_f64_f64(a, which, hip_stream);
+    };
+    int rc = go(0);
+    if (rc) return fail(rc == -1 ? "lin: the launch does not fit" : "lin: launch failed", -2);
+    // the scratch state was written behind the batch's back: whatever its stashes hold is stale
+    if (a.d.xfrc) l->scr->xfrc_on = 1;
+    if ((rc = dmc_batch_invalidate_async(l->scr, hip_stream))) return rc;
+    if (fan_only) return 0;
+    if ((rc = dmc_batch_step(l->scr, l->nstep, 0, hip_stream))) return rc;
+    rc = go(1);
+    if (rc) return fail(rc == -1 ? "lin: the launch does not fit" : "lin: launch failed", -2);
+    return 0;
+  };
+  if (l->src->precision == 64) return run(double(), double());
+  return l->scr->precision == 64 ? run(float(), double()) : run(float(), float());
+}
+extern "C" int dmc_lin_transition(dmc_lin* l, int first_env, int nenv, void* A, void* Bm, void* C, void* D, void* hip_stream) {
+  return lin_run(l, first_env, nenv, A, Bm, C, D, hip_stream, false);
+}
+extern "C" int dmc_lin_fan_out(dmc_lin* l, int first_env, int nenv, void* hip_stream) {
+  return lin_run(l, first_env, nenv, nullptr, nullptr, nullptr, nullptr, hip_stream, true);
+}

@@ -390,6 +390,64 @@ def differentiate_pos(c, qvel, dt, qpos1, qpos2):
       qvel[d] = (qpos2[a] - qpos1[a]) / dt
 
 
+def transition_fd(c, state, step, eps, centered, ctrlrange=None):
+  """mjd_transitionFD for one environment: (A, B, C, D) of x' ~ A dx + B du, y ~ C dx + D du by finite differences, with
+  x = [dq (nv), qvel (nv), act (na)].  `state`: dict(qpos, qvel, act, ctrl) at the nominal point; `step(qpos, qvel, act,
+  ctrl)` returns (qpos', qvel', act', sensordata) of one transition from that state, everything else held at the nominal
+  values by the caller.  Positions are nudged with integrate_pos and differenced with differentiate_pos; a control is
+  nudged only where ctrl and ctrl +- eps lie inside `ctrlrange` (default: the model's) of a ctrllimited actuator -- central
+  with both nudges, one-sided against the nominal next state with one, a zero column with none; not centred: the forward
+  nudge, or the backward one where the forward one is out.  The batch form is linearize.BatchLinearization."""
+  nv, na, nu = int(c.nv), int(c.na), int(c.nu)
+  nx = 2 * nv + na
+  base = [np.array(state[k], dtype=np.float64).ravel() for k in ('qpos', 'qvel', 'act', 'ctrl')]
+  cr = np.asarray(c.actuator_ctrlrange if ctrlrange is None else ctrlrange, dtype=np.float64).reshape(-1, 2)
+
+  def nudged(j, h):
+    q, v, a, u = (x.copy() for x in base)
+    if j < nv:
+      dq = np.zeros(nv)
+      dq[j] = 1.0
+      integrate_pos(c, q, dq, h)
+    elif j < 2 * nv:
+      v[j - nv] += h
+    elif j < nx:
+      a[j - 2 * nv] += h
+    else:
+      u[j - nx] += h
+    return step(q, v, a, u)
+
+  def quotient(hi, lo, h):
+    dq = np.zeros(nv)
+    differentiate_pos(c, dq, h, lo[0], hi[0])
+    return np.concatenate([dq, (hi[1] - lo[1]) / h, (hi[2] - lo[2]) / h]), (hi[3] - lo[3]) / h
+
+  nominal = None
+  cols, sens = [], []
+  for j in range(nx + nu):
+    fwd, back = True, bool(centered)
+    if j >= nx and int(c.actuator_ctrllimited[j - nx]):
+      u, (lo, hi) = base[3][j - nx], cr[j - nx]
+      inside = lambda x: lo <= x <= hi      # pylint: disable=cell-var-from-loop
+      fwd = inside(u) and inside(u + eps)
+      back = (bool(centered) or not fwd) and inside(u) and inside(u - eps)
+    if (fwd != back or not (fwd or back)) and nominal is None:
+      nominal = step(*(x.copy() for x in base))
+    if fwd and back:
+      col = quotient(nudged(j, eps), nudged(j, -eps), 2 * eps)
+    elif fwd:
+      col = quotient(nudged(j, eps), nominal, eps)
+    elif back:
+      col = quotient(nominal, nudged(j, -eps), eps)
+    else:
+      col = (np.zeros(nx), np.zeros_like(nominal[3]))
+    cols.append(col[0])
+    sens.append(col[1])
+  AB = np.stack(cols, axis=1)
+  CD = np.stack(sens, axis=1)
+  return AB[:, :nx], AB[:, nx:], CD[:, :nx], CD[:, nx:]
+
+
 def mass_matrix(c, xpos, xmat, xipos, ximat, xanchor, xaxis):
   """Dense joint-space inertia M(q) (what mj_crb leaves in mjData.M) from world-frame body Jacobians:
   M = sum_b m_b Jp_b' Jp_b + Jr_b' (R_b I_b R_b') Jr_b + diag(dof_armature)."""

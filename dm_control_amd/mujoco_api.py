@@ -1565,6 +1565,45 @@ def mj_differentiatePos(m, qvel, dt, qpos1, qpos2):
                               np.asarray(qpos2, dtype=np.float64))
 
 
+def mjd_transitionFD(m, d, eps, flg_centered, A, B, C, D):
+  """mujoco.mjd_transitionFD for one environment: A (nx, nx), B (nx, nu), C (nsensordata, nx), D (nsensordata, nu) of the
+  step's finite-difference linearisation, nx = 2 nv + na; any of them may be None.  Host numpy over this seam's own mj_step,
+  one launch per column (host_data.transition_fd); `d` is left as it was found: qpos, qvel, act, ctrl, qacc_warmstart and
+  time are put back.  C and D are the derivatives of the sensordata the step writes.  The batch form, every column of every
+  environment in one launch, is linearize.BatchLinearization."""
+  _check(m, d)
+  c = m._c
+  if not float(eps) > 0:
+    raise FatalError('mjd_transitionFD: eps must be positive')
+  nx, nu, ns = 2 * c.nv + c.na, c.nu, c.nsensordata
+  outs = ((A, (nx, nx), 'A'), (B, (nx, nu), 'B'), (C, (ns, nx), 'C'), (D, (ns, nu), 'D'))
+  for a, shape, name in outs:
+    if a is not None and np.asarray(a).size != shape[0] * shape[1]:
+      raise FatalError('mjd_transitionFD: %s must have %d x %d entries' % ((name,) + shape))
+  names = ('qpos', 'qvel', 'act', 'ctrl', 'qacc_warmstart')
+  keep = {k: np.array(getattr(d, k), dtype=np.float64) for k in names}
+  time = d.time
+
+  def put(qpos, qvel, act, ctrl):
+    for k, v in zip(names, (qpos, qvel, act, ctrl, keep['qacc_warmstart'])):
+      if v.size:
+        getattr(d, k)[...] = v.reshape(keep[k].shape)
+    d.time = time
+
+  def step(qpos, qvel, act, ctrl):
+    put(qpos, qvel, act, ctrl)
+    mj_step(m, d)
+    return tuple(np.array(getattr(d, k), dtype=np.float64).ravel() for k in ('qpos', 'qvel', 'act', 'sensordata'))
+
+  try:
+    res = host_data.transition_fd(c, keep, step, float(eps), bool(flg_centered), np.asarray(m.actuator_ctrlrange, dtype=np.float64))
+  finally:
+    put(*(keep[k].ravel() for k in names[:4]))
+  for (a, shape, _), r in zip(outs, res):
+    if a is not None:
+      np.asarray(a).reshape(shape)[...] = r
+
+
 def mj_subtreeVel(m, d):
   """legacy_base.py:148,186: the device serves subtree velocities to its sensors itself; the mjData arrays are derived on
   the host whenever they have been handed out."""
