@@ -43,6 +43,9 @@ DYN_EXPORTS = ['dmc_dyn_create', 'dmc_dyn_mass_matrix', 'dmc_dyn_bias', 'dmc_dyn
 # include/dmc_lin.h (batched linearisation: csrc/lin_kernels.hip)
 LIN_EXPORTS = ['dmc_lin_create', 'dmc_lin_transition', 'dmc_lin_fan_out', 'dmc_lin_warnings', 'dmc_lin_info', 'dmc_lin_destroy']
 
+# include/dmc_con.h (batched contact wrenches: csrc/con_kernels.hip)
+CON_EXPORTS = ['dmc_con_create', 'dmc_con_wrench', 'dmc_con_net', 'dmc_con_warmstart', 'dmc_con_info', 'dmc_con_destroy']
+
 _lib = None
 
 
@@ -181,6 +184,14 @@ def lib():
     L.dmc_lin_info.argtypes = [vp, vp]
     L.dmc_lin_destroy.argtypes = [vp]
     L.dmc_lin_destroy.restype = None
+  if hasattr(L, 'dmc_con_create'):
+    L.dmc_con_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    L.dmc_con_wrench.argtypes = [vp, vp, vp]
+    L.dmc_con_net.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.dmc_con_warmstart.argtypes = [vp, ci, vp]
+    L.dmc_con_info.argtypes = [vp, vp]
+    L.dmc_con_destroy.argtypes = [vp]
+    L.dmc_con_destroy.restype = None
   _lib = L
   return L
 

@@ -54,9 +54,12 @@ _UNITS = [
     # for the precision pairs fp64/fp64, fp32 source/fp64 scratch, fp32/fp32); no contraction: the fp64 instantiation
     # rounds like the host build of the same header (the tests' emulation)
     ('lin_kernels.hip', ['-ffp-contract=off'], ['lin_core.h', 'step_defs.h', 'step_math.h', '../../include/dmc_model_layout.h']),
-    # (the ray, distance, Jacobian, dynamics and linearisation entry points' headers -- ray_core.h, dmc_ray.h, dist_core.h,
-    # dmc_dist.h, jac_core.h, dmc_jac.h, dyn_core.h, dmc_dyn.h, lin_core.h, dmc_lin.h -- reach the staleness check through
-    # _own_includes)
+    # batched contact wrenches (fp32 and fp64: the world wrench per contact slot, the net wrench per (environment, target));
+    # no contraction: the fp64 instantiation rounds like the host build of the same header (the tests' emulation)
+    ('con_kernels.hip', ['-ffp-contract=off'], ['con_core.h', 'step_defs.h', '../../include/dmc_model_layout.h']),
+    # (the ray, distance, Jacobian, dynamics, linearisation and contact entry points' headers -- ray_core.h, dmc_ray.h,
+    # dist_core.h, dmc_dist.h, jac_core.h, dmc_jac.h, dyn_core.h, dmc_dyn.h, lin_core.h, dmc_lin.h, con_core.h, dmc_con.h --
+    # reach the staleness check through _own_includes)
     ('dmc_api.hip', [], list(STEP_SOURCES) + ['camera_core.h']),
 ]
 

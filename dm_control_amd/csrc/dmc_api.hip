@@ -2269,3 +2269,130 @@ extern "C" int dmc_lin_transition(dmc_lin* l, int first_env, int nenv, void* A, 
 extern "C" int dmc_lin_fan_out(dmc_lin* l, int first_env, int nenv, void* hip_stream) {
   return lin_run(l, first_env, nenv, nullptr, nullptr, nullptr, nullptr, hip_stream, true);
 }
+
+// ---- batched contact wrenches (con_core.h, con_kernels.hip; include/dmc_con.h) -------------------------------------
+#include "../../include/dmc_con.h"
+#include "con_core.h"
+struct dmc_con {
+  dmc_batch* b;
+  std::vector<void*> dev_bufs;      // dev_alloc / dev_free_all
+  int ntarget, words, about, nconmax;
+  int* d_head;
+  uint32_t* d_masks;
+  void* d_warm;      // (nv, B) reals: the warm start across a refresh (dmc_con_warmstart)
+};
+extern "C" int dmc_con_create(dmc_batch* b, const dmc_con_tables* tb, dmc_con** out) {
+  if (!b || !tb || !out || !tb->body || !tb->masks) return fail("null argument");
+  *out = nullptr;
+  const HostModel& m = b->model->hm;
+  const int T = tb->ntarget, W = tb->words, nconmax = b->tb.L.d.nconmax;
+  if (nconmax < 1) return fail("con: the batch holds no contacts (nconmax == 0)");
+  if (T < 1) return fail("con: at least one target is needed");
+  if (T > kConMaxTargets) return fail("con: " + std::to_string(T) + " targets, at most " + std::to_string(kConMaxTargets) + " per object");
+  if (tb->ngeom != m.ngeom || W != con_words(m.ngeom)) return fail("con: the masks are not sized for the model's " + std::to_string(m.ngeom) + " geoms");
+  if (W < 1 || W > kConMaxWords) return fail("con: a model of " + std::to_string(m.ngeom) + " geoms does not fit the mask (at most " + std::to_string(32*kConMaxWords) + ")");
+  if (tb->about < CON_ABOUT_COM || tb->about > CON_ABOUT_WORLD) return fail("con: about must be 0 (com), 1 (origin) or 2 (world)");
+  std::vector<int> head((size_t)T*kConHead, 0);
+  for (int t = 0; t < T; t++) {
+    const std::string who = "con: target " + std::to_string(t) + ": ";
+    if (tb->body[t] < 0 || tb->body[t] >= m.nbody) return fail(who + "body id outside the model");
+    const uint32_t* S = tb->masks + (size_t)t*2*W;
+    bool any = false;
+    for (int k = 0; k < 2*W; k++) {
+      const int w = k % W, bits = m.ngeom - 32*w;      // bits of this word that name a geom
+      if (bits < 32 && (S[k] >> bits)) return fail(who + "a mask bit names a geom outside the model");
+      any = any || (k < W && S[k]);
+    }
+    if (!any) return fail(who + "the set of geoms is empty");
+    head[(size_t)t*kConHead] = tb->body[t];
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  dmc_con* c = new dmc_con();      // (zeroed)
+  c->b = b; c->ntarget = T; c->words = W; c->about = tb->about; c->nconmax = nconmax;
+  int rc = dev_alloc(c, &c->d_head, sizeof(int)*head.size(), false, "con head table", head.data());
+  rc = rc ? rc : dev_alloc(c, &c->d_masks, sizeof(uint32_t)*(size_t)T*2*W, false, "con masks", tb->masks);
+  rc = rc ? rc : dev_alloc(c, &c->d_warm, std::max<size_t>(1, (size_t)m.nv)*b->B*b->elem, true, "con warm start");
+  if (rc) { dmc_con_destroy(c); return rc; }
+  *out = c;
+  return 0;
+}
+extern "C" void dmc_con_destroy(dmc_con* c) {
+  if (!c) return;
+  dev_free_all(c);
+  delete c;
+}
+static int con_need(const dmc_con* c, int local) {
+  return OUT_CONTACT | (c->about == CON_ABOUT_COM ? OUT_XIPOS : c->about == CON_ABOUT_ORIGIN ? OUT_XPOS : 0) | (local ? OUT_XMAT : 0);
+}
+extern "C" int dmc_con_info(const dmc_con* c, int* info) {
+  if (!c || !info) return fail("null argument");
+  const int v[8] = {c->b->B, c->b->precision, c->ntarget, c->nconmax, kConBlock, c->words, 2*kConMaxWords*(int)sizeof(uint32_t), con_need(c, 0)};
+  for (int k = 0; k < 8; k++) info[k] = v[k];
+  return 0;
+}
+static int con_fresh(const dmc_con* c, int need) {
+  const dmc_batch* b = c->b;
+  if ((b->outmask & b->launched_mask & need) == need) return 0;
+  return fail("con: the batch's output mask lacks the contact arrays (OUT_CONTACT) or the pose arrays `about` / `local` read (xipos / xpos / "
+              "xmat), or did when the last step / forward launch ran (or none has run yet): the arrays in device memory would be stale", -3);
+}
+template <typename T>
+static void con_fill(const dmc_con* c, ConArgs<T>* a) {
+  *a = ConArgs<T>();
+  const dmc_batch* b = c->b;
+  auto R = [&](int f) { return (const T*)b->fields[f].dev; };      // (every call: a field can be rebound)
+  auto I = [&](int f) { return (const int*)b->fields[f].dev; };
+  a->in.ncon = I(F_ncon); a->in.geom1 = I(F_contact_geom1); a->in.geom2 = I(F_contact_geom2);
+  a->in.dist = R(F_contact_dist); a->in.pos = R(F_contact_pos); a->in.frame = R(F_contact_frame); a->in.force = R(F_contact_force);
+  a->in.xpos = R(F_xpos); a->in.xipos = R(F_xipos); a->in.xmat = R(F_xmat);
+  a->in.B = (size_t)b->B; a->in.nconmax = c->nconmax; a->in.ngeom = b->model->hm.ngeom;
+  a->head = c->d_head; a->masks = c->d_masks; a->ntarget = c->ntarget; a->words = c->words; a->about = c->about;
+}
+extern "C" int dmc_con_wrench(dmc_con* c, void* wrench_out, void* hip_stream) {
+  if (!c || !wrench_out) return fail("null argument");
+  if (int rc = con_fresh(c, OUT_CONTACT)) return rc;
+  HIP_TRY(hipSetDevice(c->b->device));
+  return by_precision(c->b, [&](auto t) {
+    using T = decltype(t);
+    ConArgs<T> a;
+    con_fill(c, &a);
+    a.wrench = (T*)wrench_out;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_con_wrench_f64(a, hip_stream);
+    else rc = launch_con_wrench_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "con: the launch grid does not fit" : "con: launch failed", -2);
+    return 0;
+  });
+}
+extern "C" int dmc_con_net(dmc_con* c, int local, void* force_out, void* torque_out, void* normal_out, void* count_out, void* dist_out,
+                           void* hip_stream) {
+  if (!c) return fail("null con");
+  if (!force_out && !torque_out && !normal_out && !count_out && !dist_out) return fail("con: nothing asked for");
+  // (the pose arrays are read only for the torque's lever arm and the local frame)
+  const bool rot = local && (force_out || torque_out);
+  if (int rc = con_fresh(c, (torque_out ? con_need(c, 0) : OUT_CONTACT) | (rot ? OUT_XMAT : 0))) return rc;
+  HIP_TRY(hipSetDevice(c->b->device));
+  return by_precision(c->b, [&](auto t) {
+    using T = decltype(t);
+    ConArgs<T> a;
+    con_fill(c, &a);
+    if (!torque_out) a.about = CON_ABOUT_WORLD;      // no lever arm is needed: no pose is read
+    a.local = rot;
+    a.force = (T*)force_out; a.torque = (T*)torque_out; a.normal = (T*)normal_out; a.count = (int*)count_out; a.mindist = (T*)dist_out;
+    int rc;
+    if constexpr (std::is_same_v<T, double>) rc = launch_con_net_f64(a, hip_stream);
+    else rc = launch_con_net_f32(a, hip_stream);
+    if (rc) return fail(rc == -1 ? "con: the launch grid does not fit" : "con: launch failed", -2);
+    return 0;
+  });
+}
+extern "C" int dmc_con_warmstart(dmc_con* c, int restore, void* hip_stream) {
+  if (!c) return fail("null con");
+  dmc_batch* b = c->b;
+  const size_t bytes = (size_t)b->model->hm.nv*b->B*b->elem;
+  if (!bytes) return 0;
+  HIP_TRY(hipSetDevice(b->device));
+  void* field = b->fields[F_qacc_warmstart].dev;
+  HIP_TRY(hipMemcpyAsync(restore ? field : c->d_warm, restore ? c->d_warm : field, bytes, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+  return 0;
+}

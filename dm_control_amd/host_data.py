@@ -316,6 +316,108 @@ def object_velocity(c, kind, objid, get, local):
   return ang, lin
 
 
+CONTACT_ABOUT = ('com', 'origin', 'world')
+
+
+def _contact_ids(c, key, kind, count):
+  keys = key if isinstance(key, (list, tuple)) else [key]
+  if not keys:
+    raise ValueError('target: an empty list of %ss' % kind)
+  out = []
+  for k in keys:
+    if isinstance(k, str):
+      out.append(int(c.name2id(k, kind)))      # (ValueError: no such name)
+    elif isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+      if not 0 <= int(k) < count:
+        raise ValueError('target: %s id %d out of range (the model has %d)' % (kind, int(k), count))
+      out.append(int(k))
+    else:
+      raise ValueError('target: a %s is named by a string or an id, got %r' % (kind, k))
+  return out
+
+
+def contact_geom_set(c, spec):
+  """(mask (ngeom,) bool, named body) of a set of geoms: a geom name or id, dict(geom=..), dict(body=..) -- the body's own
+  geoms -- or dict(body=.., subtree=True) -- those of the body and everything below it.  A name, an id or a list of them.
+  The named body is the (first) body, or the (first) geom's body."""
+  if isinstance(spec, (str, int, np.integer)) and not isinstance(spec, bool):
+    spec = dict(geom=spec)
+  if not isinstance(spec, dict) or not ({'geom'} == set(spec) or ('body' in spec and set(spec) <= {'body', 'subtree'})):
+    raise ValueError('target: expected a geom name or id, dict(geom=..) or dict(body=..[, subtree=True]), got %r' % (spec,))
+  mask = np.zeros(c.ngeom, dtype=bool)
+  gbody = np.asarray(c.geom_bodyid, dtype=np.int64).reshape(-1)
+  if 'geom' in spec:
+    ids = _contact_ids(c, spec['geom'], 'geom', c.ngeom)
+    mask[ids] = True
+    return mask, int(gbody[ids[0]])
+  bodies = _contact_ids(c, spec['body'], 'body', c.nbody)
+  inb = np.zeros(c.nbody, dtype=bool)
+  inb[bodies] = True
+  if spec.get('subtree'):
+    inb = _plan(c, _subtree)[bodies].any(axis=0)
+  mask[:] = inb[gbody]
+  return mask, bodies[0]
+
+
+def contact_targets(c, targets):
+  """[dict(S, O (ngeom,) bool, body)] of a list of contact targets: a geom set (contact_geom_set) and, in a dict,
+  `other=` a second one that filters the partner geom (default: every geom).  A set without a geom is refused."""
+  targets = list(targets) if isinstance(targets, (list, tuple)) else [targets]
+  if not targets:
+    raise ValueError('targets: at least one target is needed')
+  out = []
+  for t in targets:
+    other = None
+    if isinstance(t, dict) and 'other' in t:
+      t = dict(t)
+      other = t.pop('other')
+    S, body = contact_geom_set(c, t)
+    O = np.ones(c.ngeom, dtype=bool) if other is None else contact_geom_set(c, other)[0]
+    if not S.any():
+      raise ValueError('target %r: the set of geoms is empty' % (t,))
+    out.append(dict(S=S, O=O, body=body))
+  return out
+
+
+def contact_wrenches(c, get, targets, about='com', local=False):
+  """The net contact wrench on every target from the `contact_*` arrays of the last forward: dict(force, torque
+  (..., T, 3), normal, dist (..., T), count (..., T) int32).  Contact k between geom1 and geom2 pushes geom2's body with
+  f = frame' contact_force[0:3] (torque about the contact point: frame' contact_force[3:6]) and geom1's body with the
+  opposite; a contact counts for a target with +1 when geom2 is in its set S, geom1 in its filter O and not in S, with -1 the
+  other way round.  torque is taken about the named body's xipos ('com'), xpos ('origin') or 0 ('world'); `local` rotates
+  force and torque into the named body's frame.  `get(field, *shape)` reads an mjData array as (..., *shape)."""
+  if about not in CONTACT_ABOUT:
+    raise ValueError('about must be one of %s, got %r' % (CONTACT_ABOUT, about))
+  tg = contact_targets(c, targets)
+  ncon = np.asarray(get('ncon', 1)).astype(np.int64)[..., 0]
+  g1, g2 = (np.asarray(get('contact_geom' + k, -1)).astype(np.int64) for k in '12')
+  K = g1.shape[-1]
+  frame, lf = np.asarray(get('contact_frame', K, 3, 3), dtype=np.float64), np.asarray(get('contact_force', K, 6), dtype=np.float64)
+  pos, dist = np.asarray(get('contact_pos', K, 3), dtype=np.float64), np.asarray(get('contact_dist', K), dtype=np.float64)
+  live = (np.arange(K) < ncon[..., None]) & (g1 >= 0) & (g2 >= 0) & (g1 < c.ngeom) & (g2 < c.ngeom)
+  a, b = np.where(live, g1, 0), np.where(live, g2, 0)
+  f = np.einsum('...kij,...ki->...kj', frame, lf[..., :3])
+  t = np.einsum('...kij,...ki->...kj', frame, lf[..., 3:])
+  out = dict(force=[], torque=[], normal=[], count=[], dist=[])
+  for d in tg:
+    S, O, body = d['S'], d['O'], d['body']
+    plus, minus = live & S[b] & O[a] & ~S[a], live & S[a] & O[b] & ~S[b]
+    s = plus.astype(np.float64) - minus
+    hit = plus | minus
+    r = 0.0 if about == 'world' else np.asarray(get('xipos' if about == 'com' else 'xpos', c.nbody, 3), dtype=np.float64)[..., body, :][..., None, :]
+    force = (s[..., None]*f).sum(axis=-2)
+    torque = (s[..., None]*(t + cross(pos - r, f))).sum(axis=-2)
+    if local:
+      R = np.asarray(get('xmat', c.nbody, 3, 3), dtype=np.float64)[..., body, :, :]
+      force, torque = np.einsum('...ij,...i->...j', R, force), np.einsum('...ij,...i->...j', R, torque)
+    out['force'].append(force)
+    out['torque'].append(torque)
+    out['normal'].append((hit*lf[..., 0]).sum(axis=-1))
+    out['count'].append(hit.sum(axis=-1).astype(np.int32))
+    out['dist'].append(np.where(hit, dist, np.inf).min(axis=-1) if K else np.full(ncon.shape, np.inf))
+  return {k: np.stack(v, axis=-2 if k in ('force', 'torque') else -1) for k, v in out.items()}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # derivations only MjData serves (one environment)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -300,6 +300,23 @@ class _Data:
     w = p.batch.get('contact_force').reshape(p.batch_size, -1, 2, 3)[:, contact_id]
     return w[0] if p.batch_size == 1 else w
 
+  def contact_wrenches(self, targets, about='com', local=False):
+    """The net contact wrench on every target (`contacts.BatchContacts` targets) on the host: dict(force, torque (T, 3),
+    normal, dist (T,), count (T,) int32), with a leading B for a batch.  Like `contact_force` this re-solves the constraints
+    at the current state first (one forward launch that leaves the solver's warm start alone); the device-resident form is
+    `contacts.BatchContacts`."""
+    p = self._p
+    self._upload()
+    warm = p.batch.get('qacc_warmstart')
+    p.batch.forward(False)
+    p.batch.set('qacc_warmstart', warm)      # a query must not move the solver's warm start
+    self._cache.clear()
+    self._prefetched.clear()
+    B = p.batch_size
+    get = lambda n, *shape: np.asarray(p.batch.get(n)).reshape((B,) + shape)
+    out = host_data.contact_wrenches(p.model, get, targets, about, local)
+    return {k: v[0] for k, v in out.items()} if B == 1 else out
+
   def object_velocity(self, object_id, object_type, local_frame=False):
     """6D velocity (linear, angular) of a body / xbody / geom / site, 2 x 3 (batch: B x 2 x 3);
     mj_objectVelocity (wrapper/core.py:500-525) evaluated on the host from cvel / subtree_com."""
